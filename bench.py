@@ -1,6 +1,6 @@
 """bench.py -- headline benchmark (BASELINE.json `metric`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload: push-sum on the imperfect-3D lattice with 1e9 nodes (g = 1000,
 BASELINE config 4 = C5), which fits one MI355X (46 GB of state).  A "step" is one
@@ -10,16 +10,22 @@ resident in HBM.  Before the timed region the simulation is advanced until
 every node is active (steady state: every node sends a message each round),
 then W warmup rounds; convergence is never reached inside the timed window.
 
+A plain run sets up, warms up, times the K rounds and prints the result line;
+--dump-outputs DIR then also writes what the last timed round left (dump_outputs).
+--full adds the measurements that take runs of their own: the HBM-traffic passes,
+the CPU baseline and the `akka_baseline` record (below).
+
 One JSON line on stdout (rank 0).  `roofline` is measured live: HIP events on
 the library's stream bracket every round kernel; `achieved` counts SURVEY.md
 §8(d)'s algorithmic bytes per node-round (B_ps = 34 + 4 [Imp3D] + 32 a + 8 a_x:
 71.1 B at C5's steady state, survey_bytes_per_node), and `design_*` the fewer
 bytes this design must move (no message is staged
-through HBM).  `traffic` is
+through HBM).  With --full, `traffic` is
 measured in the same run: before the bench, the workload is re-run as a child
 under three rocprofv3 --pmc passes and the round kernel's HBM bytes are read
-from the L2's request-size counters (tools/hbm_traffic.py).  `cpu_baseline` times the SRS v1 C oracle on the host cores over a
-bounded sample of the same workload (steady state, smaller lattice).
+from the L2's request-size counters (tools/hbm_traffic.py), and `cpu_baseline`
+times the SRS v1 C oracle on the host cores over a bounded sample of the same
+workload (steady state, smaller lattice).
 
 Multi-GPU (N > 1): one process per GPU, contiguous plane-aligned node slabs,
 RCCL exchange inside libgossip_hip.  Under torch.distributed.run the ranks come
@@ -78,6 +84,40 @@ def preroll(sim, population, cap=2000):
             return rounds
         rounds += len(sim.step(8))
     raise RuntimeError("activation did not complete within %d rounds" % cap)
+
+
+DUMP_WINDOWS, DUMP_WINDOW_NODES, DUMP_SEED = 64, 16384, 20240607  # 2^20 nodes x 5 float64 arrays: 40 MiB
+
+
+def dump_outputs(sim, alerts, outdir, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after its last round, as
+    float64 <name>.npy files (exact for the int32 counters, the flags and node ids
+    < 2^53): `alerts`, the alert count of every timed round (gp_step's return), and the
+    node state the last round left (gp_read_state: c, s, w, flags) with the node ids in
+    `state_index`.  A slab of more than DUMP_WINDOWS * DUMP_WINDOW_NODES nodes is
+    sampled: its first and last window and seeded-random ones between, the same
+    windows for the same arguments.  Rank r > 0 of a multi-GPU run writes <name>_rank<r>."""
+    import numpy as np
+    info = sim.info()
+    first, count = info.slab_first, info.slab_count
+    if count <= DUMP_WINDOWS * DUMP_WINDOW_NODES:
+        starts, width = np.array([first], np.int64), count
+    else:
+        width = DUMP_WINDOW_NODES
+        rng = np.random.default_rng(DUMP_SEED)
+        mid = rng.choice((count - 2 * width) // width, DUMP_WINDOWS - 2, replace=False).astype(np.int64)
+        starts = first + np.concatenate(([0], width + np.sort(mid) * width, [count - width]))
+    parts = [sim.state(int(a), int(width)) for a in starts]
+    arrays = {"alerts": np.asarray(alerts, np.float64),
+              "state_index": np.concatenate([np.arange(a, a + width, dtype=np.float64) for a in starts])}
+    for k in ("c", "s", "w", "flags"):
+        arrays["state_" + k] = np.concatenate([p[k] for p in parts]).astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 and rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + suffix + ".npy"), a)
+    log(f"[bench] rank {rank}: wrote {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MiB, "
+        f"{len(starts)} window(s) of {width} nodes, to {outdir}")
 
 
 def measure_traffic(args):
@@ -225,15 +265,21 @@ def main():
     ap.add_argument("--topology", default="Imp3D")
     ap.add_argument("--algorithm", default="push-sum")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed rounds, write their alert counts and (a fixed sample of) the node "
+                         "state the last one left as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: rocprofv3 HBM-traffic passes, CPU baseline, "
+                         "akka_baseline record")
     ap.add_argument("--cpu-nodes", type=int, default=0, help="CPU-baseline sample size (0: --nodes)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-rounds", type=int, default=3,
                     help="CPU-baseline rounds at least (a 10^9-node round takes ~16 s on 256 cores)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU-baseline OpenMP threads (0: every core in the scheduler affinity mask)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--converge", action="store_true", help="also run a fresh simulation to convergence")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 HBM-traffic passes")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the rocprofv3 HBM-traffic passes")
     ap.add_argument("--traffic-kernel", default="auto",
                     help="round-kernel name substring in the counters (auto: the kernel that writes the most)")
     ap.add_argument("--traffic-timeout", type=float, default=240.0)
@@ -248,8 +294,9 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: refusing to measure another GPU count")
-    traffic, traffic_note = None, "not measured (multi-GPU run)" if world > 1 else "not measured (--no-traffic)"
-    if world == 1 and not args.no_traffic:
+    traffic, traffic_note = None, ("not measured (multi-GPU run)" if world > 1 else
+                                   "not measured (--no-traffic)" if args.full else "not measured (plain run: see --full)")
+    if world == 1 and args.full and not args.no_traffic:
         t_tr = time.perf_counter()
         traffic, traffic_note = measure_traffic(args)
         log(f"[bench] HBM traffic passes: {time.perf_counter() - t_tr:.1f} s, "
@@ -310,6 +357,8 @@ def main():
     design_bytes = sim.alg_bytes_per_node()
     g_edge = round(P ** (1.0 / 3.0)) if args.topology in ("3D", "Imp3D") else 0
     local_nodes = sim.local_population
+    if args.dump_outputs:
+        dump_outputs(sim, got, args.dump_outputs, rank, world)
     sim.close()
 
     value = P * args.steps / elapsed
@@ -369,9 +418,9 @@ def main():
         }
     else:
         out["roofline"]["traffic_detail"] = {"method": traffic_note}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(args)
-    out["akka_baseline"] = akka_baseline()
+    out["akka_baseline"] = akka_baseline() if args.full else None
     if rank == 0 and world == 1 and args.converge:
         with Simulation(args.nodes, args.topology, args.algorithm, seed=args.seed, device=device) as s2:
             res = s2.run()
