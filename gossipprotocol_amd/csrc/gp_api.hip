@@ -1804,6 +1804,10 @@ int build_sim(gp_sim* s) {
         }
         if (const char* e = exp_env("GP_FUSE")) sl.S.fuse_finalize = sl.S.fuse_finalize ? (uint32_t)(e[0] - '0') : 0u;
         if (const char* e = exp_env("GP_STAGE_CAP")) sl.S.tile_stage_cap = (uint32_t)std::max(0, std::atoi(e));
+#ifdef GP_EXPERIMENTS
+        sl.S.tile_no_full = 0u;
+        if (const char* e = exp_env("GP_NO_FULLTILE")) sl.S.tile_no_full = e[0] == '1' ? 1u : 0u;
+#endif
         if ((rc = alloc_slab(s, sl, sl.rank))) return rc;
         sl.S.rregions = rreg;
         if (sl.S.tile_walk == 3) {  // the tile list of the per-XCD queues

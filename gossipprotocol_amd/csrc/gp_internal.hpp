@@ -247,6 +247,9 @@ struct DevState {
     uint32_t tile_walk;  // RoundArgs::walk
     uint32_t tile_wx;    // RoundArgs::wx
     uint32_t tile_stage_cap;  // RoundArgs::stage_cap (experiments build only; default: no limit)
+#ifdef GP_EXPERIMENTS
+    uint32_t tile_no_full;    // RoundArgs::no_full
+#endif
     uint32_t fuse_finalize;   // the round kernel closes its own round (single rank push-sum)
     BlockPlan bplan;          // KERNEL_BLOCK (gp_block.hip): boxes, face buffer, barrier scratch
     void* bface;
@@ -295,6 +298,9 @@ struct RoundArgs {
                     // 3: x-windows claimed from per-XCD counters (k_ps_tile)
     uint32_t wx;    // walk 2: planes per x-window
     uint32_t stage_cap;  // k_ps_tile: tiles with more in-edges take the unstaged path (tests force it)
+#ifdef GP_EXPERIMENTS
+    uint32_t no_full;    // k_ps_tile: every tile through the general (!FULL) tile body (GP_NO_FULLTILE=1)
+#endif
     uint32_t fuse;       // k_ps_tile: the last block closes the round (no k_finalize launch)
     const uint32_t* wt;  // walk 3: tile list (DevState::wtiles), XCD c's items at [wo[c], wo[c + 1])
     uint32_t wo[9];

@@ -255,6 +255,10 @@ struct TileWalk {
             rel = t;
             return true;
         }
+        // (the divisors opaque: their reciprocals are then computed here, per item, instead of being
+        // hoisted out of the caller's tile loop into VGPRs that stay live across its node phase)
+        uint32_t kp = this->kp, nwin = this->nwin, nxa = this->nxa;
+        asm volatile("" : "+s"(kp), "+s"(nwin), "+s"(nxa));
         const uint32_t pl = t / kp;  // planes of this XCD before the item's window start (approx.)
         uint32_t v = (uint32_t)((uint64_t)pl * nwin / nxa);
         if (v >= nwin) v = nwin - 1;
@@ -415,9 +419,13 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                 // in-edge q = m * TPB + wave * 64 + lane is bit `lane` of bitmap word
                 // m * 4 + wave; its message (if used) lands in slot q
                 if (SNDPF && snd_tile == ti) {  // (block-uniform) prefetched during the last tile
+                    // (the thread index opaque: the thread's LDS address in snd is then formed here, not
+                    // kept in a register across the tile loop, where it spilled)
+                    uint32_t ts = threadIdx.x;
+                    asm volatile("" : "+v"(ts));
 #pragma unroll
                     for (int m = 0; m < FU; ++m) {
-                        const uint32_t q = threadIdx.x + m * TPB;
+                        const uint32_t q = ts + m * TPB;
                         raw[m] = q < cnt ? snd[snd_off + q] : 0u;
                     }
                 } else {
@@ -556,7 +564,13 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                                                          0, DMA_ONCE);
                     }
                 }
-                if (threadIdx.x == 0) L.bits[FU * (TPB / 64)] = 0ull;
+                if (threadIdx.x == 0) {
+                    // (the zero made here: as a loop invariant it was kept in a register pair across the
+                    // tile loop, and spilled)
+                    unsigned long long z = 0ull;
+                    asm volatile("" : "+v"(z));
+                    L.bits[FU * (TPB / 64)] = z;
+                }
             }
         }
         // own (s, w): loaded with the node's lattice gathers (ahead of the staging
@@ -572,14 +586,24 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
         // (s, w) across every wave's ends, slot k: node T + k*TPB + 64 wave - 1 and + 64
         // (clamped into the node arrays; used only where that neighbour sent)
         if (lane < 2u * NPT) {
-            int64_t jn = (int64_t)T + (int64_t)((lane >> 1) * TPB + wv * 64u) + ((lane & 1u) ? 64 : -1);
+            // (the lane opaque: its part of the index is then computed here, by 8 lanes per tile, not
+            // kept in a register pair across the tile loop)
+            uint32_t zl = lane;
+            asm volatile("" : "+v"(zl));
+            int64_t jn = (int64_t)T + (int64_t)((zl >> 1) * TPB + wv * 64u) + ((zl & 1u) ? 64 : -1);
             if (jn < (int64_t)a.ext_lo) jn = a.ext_lo;
             if (jn > (int64_t)a.ext_hi) jn = a.ext_hi;
             __builtin_amdgcn_global_load_lds((gvoid_t*)(swc + jn), (lvoid_t*)&L.zb[wv][0][0], 16, 0, 0);
         }
         // the tile's in-degrees, a nibble per node (512 bytes; the slab's arrays
         // cover whole tiles, ids outside the slab are 0)
-        if (TOPO == IMP3D) dma_copy<DMA_ONCE>(L.ind, reinterpret_cast<const char*>(a.ind4 + T / 2), TILE / 2);
+        if (TOPO == IMP3D) {
+            // (the tile's base opaque: otherwise a.ind4 + the thread's offset is kept as a 64-bit
+            // address across the tile loop, and spilled)
+            const uint8_t* ip = a.ind4 + T / 2;
+            asm volatile("" : "+s"(ip));
+            dma_copy<DMA_ONCE>(L.ind, reinterpret_cast<const char*>(ip), TILE / 2);
+        }
         if (dyn && threadIdx.x == 0) L.qn[it & 1] = claim;
         __builtin_amdgcn_s_setprio(0);
         __syncthreads();  // staging copies, in-edge bitmap and gathered messages retired
@@ -628,6 +652,24 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
             }
         }
 
+        // The node phase, the direction draws and the byte write-out are compiled twice.  FULL: the
+        // tile lies wholly inside the slab and (Imp3D) is staged and not `wide` -- all but the
+        // slab's first and last tile and the ~4e-5 of tiles above the staging cap.  Every node
+        // is then valid: no range tests, no clamp of the own index, no loads for j +- 1 outside
+        // the range, only the bitmap-window in-edge walk; the z +- 1 sender tests take the
+        // neighbour lanes' direction byte by DPP.  !FULL serves every other tile.
+        bool full = j0 == T && j1 == T + TILE && (TOPO != IMP3D || (staged && !wide));  // block-uniform
+#ifdef GP_EXPERIMENTS
+        if (a.no_full) full = false;  // GP_NO_FULLTILE=1: every tile through the general body (A/B, parity tests)
+#endif
+        auto tile_body = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+        // the thread index is opaque to each body: what a body derives from it (lane tests, byte
+        // offsets, per-thread address parts) is computed once per tile, not hoisted out of the tile
+        // loop into registers that stay live across the in-edge pass (two bodies' worth spilled)
+        uint32_t tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const uint32_t lane = tid & 63u, wv = tid >> 6;
         // per node, 16 bits (two nodes per word): bits 0-5 lattice mask, bit 6 draw a
         // next-round direction, bits 7-10 the node byte's flag bits 3-6
         uint32_t pend[(NPT + 1) / 2];
@@ -638,7 +680,7 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
             // scalar), advanced by TPB per slot.  A wave whose 64 nodes are all
             // interior (no lattice boundary; ~93 % of waves at g = 1000) takes mask =
             // 63 without per-lane coordinates; the others compute each node's mask.
-            const uint32_t wbase = __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u);
+            const uint32_t wbase = __builtin_amdgcn_readfirstlane(tid & ~63u);
             uint32_t wcx = 0, wcy = 0, wcz = 0;
             if (TOPO != LINE) {
                 const uint32_t jw = T + wbase;
@@ -664,7 +706,7 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                     epre[h] = edeg[h] = 0u;
                     if (TOPO == IMP3D) {
                         const int k = k0 + h;
-                        const uint32_t jl = k * TPB + threadIdx.x;
+                        const uint32_t jl = k * TPB + tid;
                         const uint32_t d = (lds_byte(L.ind, jl >> 1) >> ((jl & 1u) * 4u)) & 15u;
                         uint32_t ex = mbcnt64(__ballot(d & 1u)) + 2u * mbcnt64(__ballot(d & 2u));
                         if (__ballot(d >= 4u)) ex += 4u * mbcnt64(__ballot(d & 4u)) + 8u * mbcnt64(__ballot(d & 8u));
@@ -679,7 +721,7 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
 #pragma unroll
                 for (int h = 0; h < NG; ++h) {
                     const int k = k0 + h;
-                    const uint32_t j = T + k * TPB + threadIdx.x;
+                    const uint32_t j = T + k * TPB + tid;
                     if (TOPO != LINE && k > 0) {
                         wcz += TPB;
                         if (wcz >= G.g) {
@@ -713,19 +755,32 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                         const uint32_t bxp = lds_byte(L.xp, (mask & 2u) ? j + G.g2 - b_xp : 0u);
                         const uint32_t byp = lds_byte(L.rows, (mask & 4u) ? jr + G.g : jr);
                         const uint32_t bym = lds_byte(L.rows, (mask & 8u) ? jr - G.g : jr);
-                        const uint32_t bzp = lds_byte(L.rows, (mask & 16u) ? jr + 1 : jr);
-                        const uint32_t bzm = lds_byte(L.rows, (mask & 32u) ? jr - 1 : jr);
-                        from = ((bxm & DIR_MASK) == 1u ? 1u : 0u) | ((bxp & DIR_MASK) == 0u ? 2u : 0u) |
+                        uint32_t bzp, bzm;
+                        if constexpr (FULL) {
+                            // z +- 1 are lanes +- 1: their direction byte by DPP (every lane is
+                            // active in a full tile); across the wave's ends one LDS byte: lane 63
+                            // reads j + 1, lane 0 j - 1 (index kept >= 0: node 0 has no z - 1), the
+                            // lanes between read j - 1 as well and do not use it
+                            const uint32_t be = lds_byte(L.rows, lane == 63u ? jr + 1u : max(jr, 1u) - 1u);
+                            bzp = (uint32_t)__builtin_amdgcn_mov_dpp((int)gbv, 0x130, 0xF, 0xF, true);
+                            bzm = (uint32_t)__builtin_amdgcn_mov_dpp((int)gbv, 0x138, 0xF, 0xF, true);
+                            if (lane == 63u) bzp = be;
+                            if (lane == 0u) bzm = be;
+                        } else {
+                            bzp = lds_byte(L.rows, (mask & 16u) ? jr + 1 : jr);
+                            bzm = lds_byte(L.rows, (mask & 32u) ? jr - 1 : jr);
+                        }
+                        from =((bxm & DIR_MASK) == 1u ? 1u : 0u) | ((bxp & DIR_MASK) == 0u ? 2u : 0u) |
                                ((byp & DIR_MASK) == 3u ? 4u : 0u) | ((bym & DIR_MASK) == 2u ? 8u : 0u) |
                                ((bzp & DIR_MASK) == 5u ? 16u : 0u) | ((bzm & DIR_MASK) == 4u ? 32u : 0u);
                         from &= mask;
                     }
-                    if (!(j >= j0 && j < j1)) from = 0u;
+                    if (!FULL && !(j >= j0 && j < j1)) from = 0u;
                     gst[h] = gbv | (mask << 8) | (from << 14) | (edeg[h] << 20);
                     // unconditional (index clamped into the tile's valid range; invalid lanes'
                     // values are never used): a load under a branch made the compiler wait
                     // for it before issuing the lattice gathers
-                    own[k] = swc[min(max(j, j0), j1 - 1u)];
+                    own[k] = swc[FULL ? j : min(max(j, j0), j1 - 1u)];
 #pragma unroll
                     for (uint32_t d = 0; d < NDG; ++d)
                         m[h][d] = ld_sw(swc + ((from >> d) & 1u ? nbr<TOPO>(j, d, G) : a.ext_hi));
@@ -737,15 +792,15 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
 #pragma unroll
                 for (int h = 0; h < NG; ++h) {
                     const int k = k0 + h;
-                    const uint32_t jl = k * TPB + threadIdx.x;
+                    const uint32_t jl = k * TPB + tid;
                     const uint32_t j = T + jl;
-                    const bool valid = j >= j0 && j < j1;
+                    const bool valid = FULL || (j >= j0 && j < j1);
                     // Imp3D, staged tile: the node's window of the used-in-edge bitmap and its first
                     // used in-edge's message, read from LDS while the slot's loads are in flight (the
                     // fold needed both after the loads, one LDS round trip after the other).  A node's
                     // in-edges fit one 32-bit window (in-degree <= 14 outside `wide` tiles).
                     uint32_t pwin = 0u, pqb = 0u;
-                    if (TOPO == IMP3D && staged && !wide) {
+                    if (TOPO == IMP3D && (FULL || (staged && !wide))) {
                         const uint32_t* bw = reinterpret_cast<const uint32_t*>(L.bits);
                         pqb = epre[h];
                         const uint32_t nd = gst[h] >> 20;
@@ -764,9 +819,9 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                         if (lane == 63u) zP = L.zb[wv][k][1];
                         if (lane == 0u) zM = L.zb[wv][k][0];
                         if (!((from >> dP) & 1u)) zP = make_double2(0.0, 0.0);
-                        else if (lane != 63u && j + 1u >= j1) zP = ld_sw(swc + j + 1);
+                        else if (!FULL && lane != 63u && j + 1u >= j1) zP = ld_sw(swc + j + 1);
                         if (!((from >> dM) & 1u)) zM = make_double2(0.0, 0.0);
-                        else if (lane != 0u && j <= j0) zM = ld_sw(swc + j - 1);
+                        else if (!FULL && lane != 0u && j <= j0) zM = ld_sw(swc + j - 1);
                     }
                     // every load of the slot retired here, on all paths: the slot's state store is then the
                     // only memory operation the next slot's loads could wait for, and they do not
@@ -805,11 +860,11 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                         }
                         if (TOPO == IMP3D) {
                             uint32_t e_b = e_lo + epre[h], e_e = e_b + (gst[h] >> 20);
-                            if (wide) {
+                            if (!FULL && wide) {
                                 e_b = a.in_off[j];
                                 e_e = a.in_off[j + 1];
                             }
-                            if (staged && !wide) {
+                            if (FULL || (staged && !wide)) {
                                 // the window and first message read above; the rest set bit by set
                                 // bit (ascending sender = canonical order), edge q's message at slot q
                                 uint32_t win = pwin;
@@ -901,12 +956,12 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
         {
             uint32_t node[NPT], x[NPT], y[NPT];
 #pragma unroll
-            for (int k = 0; k < NPT; ++k) node[k] = T + k * TPB + threadIdx.x;
+            for (int k = 0; k < NPT; ++k) node[k] = T + k * TPB + tid;
             philox2_batch<NPT>(node, r + 1, S_PUSHSUM, a.k0, a.k1, x, y);
 #pragma unroll
             for (int k = 0; k < NPT; ++k) {
-                const uint32_t jl = k * TPB + threadIdx.x;
-                const bool valid = node[k] >= j0 && node[k] < j1;
+                const uint32_t jl = k * TPB + tid;
+                const bool valid = FULL || (node[k] >= j0 && node[k] < j1);
                 const uint32_t pk = pend[k >> 1] >> (16 * (k & 1));
                 const uint32_t mask = pk & 63u;
                 uint32_t dir = DIR_NONE;
@@ -915,7 +970,7 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                 if (TOPO == IMP3D) {
                     const unsigned long long bits = __ballot(valid && dir == DIR_RANDOM);
                     if (lane == 0) {  // the slab's first tile may start below lo: no word there
-                        const int64_t wi = (int64_t)((T + k * TPB + (threadIdx.x & ~63u)) >> 6) - (int64_t)(a.lo >> 6);
+                        const int64_t wi = (int64_t)((T + k * TPB + (tid & ~63u)) >> 6) - (int64_t)(a.lo >> 6);
                         if (wi >= 0) a.rbn[wi] = bits;
                     }
                 }
@@ -923,15 +978,18 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
         }
         __syncthreads();
         // node bytes out as words (allocations are padded past P)
-        for (uint32_t w = threadIdx.x; w < (uint32_t)(TILE / 4); w += TPB) {
+        for (uint32_t w = tid; w < (uint32_t)(TILE / 4); w += TPB) {
             const uint32_t jw = T + w * 4;
-            if (jw >= j0 && jw + 4 <= j1) {
+            if (FULL || (jw >= j0 && jw + 4 <= j1)) {
                 st_stream(reinterpret_cast<uint32_t*>(a.nbn + T) + w, L.out[w]);
             } else {
                 for (uint32_t b = 0; b < 4; ++b)
                     if (jw + b >= j0 && jw + b < j1) a.nbn[jw + b] = reinterpret_cast<const uint8_t*>(L.out)[w * 4 + b];
             }
         }
+        };
+        if (full) tile_body(std::true_type{});
+        else tile_body(std::false_type{});
         // no barrier here: the next tile's in-edge pass and staging copies write
         // bits / msg / rows / xm / xp / off, none of which this byte output reads,
         // and its node phase writes L.out only after its staging barrier
@@ -953,7 +1011,11 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
 // Uses L.red; the barrier also orders the block's last byte output before any
 // later LDS reuse.
 __device__ __forceinline__ void block_counts(uint32_t (*red)[TPB / 64], uint32_t& x, uint32_t& y) {
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    // (the thread index opaque: lane and wave are then formed here, at the kernel's end, not kept
+    // in registers across the caller's tile loop)
+    uint32_t tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const uint32_t lane = tid & 63u, wv = tid >> 6;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         x += __shfl_xor(x, o, 64);
@@ -1228,6 +1290,9 @@ RoundArgs make_round_args(const DevState& S, uint32_t round) {
     a.ntiles = tiles_for(S.lo, S.nloc);
     a.walk = S.tile_walk;
     a.stage_cap = S.tile_stage_cap;
+#ifdef GP_EXPERIMENTS
+    a.no_full = S.tile_no_full;
+#endif
     a.wx = S.tile_wx;
     a.fuse = S.fuse_finalize;
     a.wt = S.wtiles;
