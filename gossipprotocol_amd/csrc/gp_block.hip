@@ -27,16 +27,13 @@
 // layout.  Every barrier wait has a time limit: a grid that is not co-resident
 // (hipLaunchCooperativeKernel refuses such a launch) or a lost block sets `err` and
 // every block leaves -- the batch fails loudly instead of hanging the device.
-#include <algorithm>
-
+#include "gp_block_plan.hpp"
 #include "gp_internal.hpp"
 
 namespace gp {
 
 namespace {
 
-constexpr int BK_THREADS = 1024;
-constexpr int BK_NPT = 5;  // nodes per thread: boxes of at most 5120 nodes
 constexpr int EPOCH = BLOCK_EPOCH;  // rounds between grid barriers
 
 struct BlockArgs {
@@ -478,40 +475,7 @@ __global__ __launch_bounds__(BK_THREADS) void k_ps_block(BlockArgs a) {
 }
 
 // ---------------------------------------------------------------- host side
-// The box grid of a g^3 lattice for `cus` workgroups: the most boxes (at most one per
-// CU, a box of at most BK_NPT * 1024 nodes) with the smallest largest box, whose LDS
-// (17 bytes per node and per halo node) fits; false if none does.
-bool block_plan(uint32_t g, int cus, BlockPlan& p) {
-    bool found = false;
-    uint64_t best_v = ~0ull;
-    for (uint32_t nx = 1; nx <= g && nx <= (uint32_t)cus; ++nx)
-        for (uint32_t ny = 1; ny <= g && nx * ny <= (uint32_t)cus; ++ny)
-            for (uint32_t nz = 1; nz <= g && nx * ny * nz <= (uint32_t)cus; ++nz) {
-                const uint64_t bx = (g + nx - 1) / nx, by = (g + ny - 1) / ny, bz = (g + nz - 1) / nz;
-                const uint64_t v = bx * by * bz;
-                const uint64_t f = std::max(by * bz, std::max(bx * bz, bx * by));
-                const uint64_t ns = v + 6 * f + 1;
-                const uint64_t lds = 16 * ns + ((ns + 3) & ~3ull) + ((v + 3) & ~3ull) + 4 * v + 64;
-                if (v > (uint64_t)BK_NPT * BK_THREADS || lds > 150 * 1024 || bx > 1023 || by > 1023 || bz > 1023)
-                    continue;
-                // estimated round time: node slots per thread (ceil(v / 1024)) plus a grid barrier
-                // (~3 slots) when there are several boxes; then the fewest boxes (less face traffic)
-                const uint64_t nbk = (uint64_t)nx * ny * nz;
-                const uint64_t key = (((v + BK_THREADS - 1) / BK_THREADS + (nbk > 1 ? 3 : 0)) << 32) | nbk;
-                if (!found || key < best_v) {
-                    found = true;
-                    best_v = key;
-                    p.nbx = nx;
-                    p.nby = ny;
-                    p.nbz = nz;
-                    p.vmax = (uint32_t)v;
-                    p.fmax = (uint32_t)f;
-                    p.lds = (uint32_t)lds;
-                }
-            }
-    return found;
-}
-
+// (the box grid itself: block_plan, gp_block_plan.hpp)
 size_t block_face_bytes(const BlockPlan& p) {
     const size_t nb = (size_t)p.nbx * p.nby * p.nbz;
     return 2 * nb * 6 * p.fmax * (16 + 4);
@@ -533,8 +497,7 @@ hipError_t launch_round_block(const DevState& S, const BlockPlan& p, uint32_t r0
     a.fs = static_cast<double2*>(face);
     a.fb = reinterpret_cast<uint32_t*>(a.fs + 2 * nb * 6 * p.fmax);
     // scratch (words): [0] barrier (groups arrived), [1] error flag, [16 (1 + grp)] the arrivals
-    // of block group grp (a 64-byte line each), [144, 144 + 12 EPOCH) 3 x EPOCH x 2 accumulators,
-    // then a 64-byte line of step flags per box
+    // of block group grp (a 64-byte line each), [144, 144 + 12 EPOCH) 3 x EPOCH x 2 accumulators
     a.bar = static_cast<unsigned int*>(scratch);
     a.err = a.bar + 1;
     a.acc = reinterpret_cast<unsigned long long*>(a.bar + 144);

@@ -7,6 +7,7 @@
 
 #include <vector>
 
+#include "gp_block_plan.hpp"
 #include "gp_device.hpp"
 
 namespace gp {
@@ -170,13 +171,6 @@ struct XHdr {
 };
 static_assert(sizeof(XHdr) == 16, "header words move as 16-byte loads");
 
-// KERNEL_BLOCK (gp_block.hip): the lattice cut into nbx * nby * nbz boxes, one per workgroup.
-struct BlockPlan {
-    uint32_t nbx, nby, nbz;  // boxes per axis
-    uint32_t vmax, fmax;     // largest box (nodes) and largest face
-    uint32_t lds;            // dynamic LDS bytes per workgroup
-};
-
 // Node state in HBM (structure of arrays, single GPU / one slab).
 struct DevState {
     Geom G;
@@ -311,8 +305,7 @@ struct RoundArgs {
 enum KernelVariant : int { KERNEL_TILE = 1, KERNEL_COL = 2, KERNEL_BLOCK = 3 };
 
 // ---- LDS-resident push-sum on a small 3D lattice (gp_block.hip): one cooperative launch
-// per batch of rounds (BlockPlan above DevState)
-bool block_plan(uint32_t g, int cus, BlockPlan& p);
+// per batch of rounds (BlockPlan and block_plan: gp_block_plan.hpp)
 size_t block_face_bytes(const BlockPlan& p);
 hipError_t block_kernel_setup(const BlockPlan& p);
 bool block_plan_resident(const BlockPlan& p, int cus);

@@ -501,8 +501,10 @@ def test_round_close_parity(fuse, n, topo, seed, rounds, chk, monkeypatch):
 BLOCK_CASES = [  # (num_nodes, seed, rounds, checkpoint): 3D push-sum, the LDS-resident kernel
     (1000, 3, 3000, 1000),        # one box, no grid barrier; through convergence
     (27000, 5, 400, 100),         # several boxes
-    (8000, 7, 40000, 997),        # two boxes through convergence: batches and the converging
-                                  # round cut epochs (16 rounds) mid-way -> checkpoint replay
+    (8000, 7, 40000, 997),        # eight boxes, 64-round epochs, through convergence: R % 64 != 0
+                                  # and the last launch's share of R is no multiple of 64 either
+                                  # (asserted below), so it converges inside an epoch -> checkpoint
+                                  # replay (the other replay cases: test_gpu_block_kernel.py)
     (1000000, 1, 300, 150),       # C2 (g = 100): one box per CU
     (1030301, 2, 120, 60),        # g = 101: uneven boxes
 ]
@@ -525,6 +527,11 @@ def test_block_kernel_parity(n, seed, rounds, chk, monkeypatch):
         assert_same_state("push-sum", sim.state(), orc.state())
         done += k
     assert sim.rounds == orc.rounds
+    if (n, seed) == (8000, 7):  # the replay case: converged, and not on an epoch's last round
+        # (every launch here starts on a multiple of 997 + 1024 j rounds; the last one, at
+        # 997 * 12 + 0 = 11964, has R - 11964 = 612 = 9 * 64 + 36 rounds: its 10th epoch replays)
+        assert orc.alerts_total >= orc.T and orc.rounds % 64 != 0
+        assert (orc.rounds - orc.rounds // chk * chk) % 64 != 0
     sim.close()
     orc.close()
 
