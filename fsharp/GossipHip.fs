@@ -63,6 +63,37 @@ extern int gp_read_state(nativeint sim, int64 first, int64 count, int32[] c, dou
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern void gp_destroy(nativeint sim)
 
+// Ensembles: one network per seed, all seeds at once (INTEGRATION.md §2.2)
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type GpMember =
+    val mutable Seed: uint64
+    val mutable Rounds: int64
+    val mutable Converged: int64
+    val mutable SeedNode: int64
+    val mutable Status: int32
+    val mutable Reserved: int32
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int64 gp_ensemble_max_nodes(int topology, int algorithm)
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gp_ensemble_create(GpConfig& cfg, uint64[] seeds, int64 nseeds, nativeint& ensemble)
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int64 gp_ensemble_step(nativeint ensemble, int64 nrounds)
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gp_ensemble_run(nativeint ensemble, [<Out>] GpMember[] members)
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gp_ensemble_members(nativeint ensemble, [<Out>] GpMember[] members)
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gp_ensemble_read_state(nativeint ensemble, int64 ``member``, int64 first, int64 count, int32[] c, double[] s, double[] w, byte[] flags)
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern void gp_ensemble_destroy(nativeint ensemble)
+
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern nativeint gp_last_error()
 

@@ -18,7 +18,7 @@ EXP_LIB_PATH = os.environ.get("GOSSIP_HIP_LIB_EXPERIMENT", EXP_LIB_PATH)
 
 GP_LINE, GP_FULL, GP_3D, GP_IMP3D = 0, 1, 2, 3
 GP_GOSSIP, GP_PUSHSUM = 0, 1
-GP_STATUS_CONVERGED, GP_STATUS_MAX_ROUNDS = 0, 1
+GP_STATUS_CONVERGED, GP_STATUS_MAX_ROUNDS, GP_STATUS_RUNNING = 0, 1, 2
 GP_FLAG_KERNEL_TIMING = 1
 GP_FLAG_VIRTUAL_RANKS = 2
 ERRORS = {-1: "GP_EINVAL", -2: "GP_ENOMEM", -3: "GP_EHIP", -4: "GP_ENCCL", -5: "GP_ESTATE", -6: "GP_ENODEV"}
@@ -44,6 +44,12 @@ class GpInfo(C.Structure):
                 ("slab_count", C.c_int64)]
 
 
+class GpMember(C.Structure):
+    """One ensemble member (gp_member)."""
+    _fields_ = [("seed", C.c_uint64), ("rounds", C.c_int64), ("converged", C.c_int64),
+                ("seed_node", C.c_int64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 # (name, restype, argtypes) for every symbol include/gossip_hip.h declares
 _vp, _i64, _i32 = C.c_void_p, C.c_int64, C.c_int32
 SIGNATURES = [
@@ -65,6 +71,13 @@ SIGNATURES = [
     ("gp_kernel_stats", _i32, [_vp, C.POINTER(C.c_double), C.POINTER(_i64), C.c_char_p, _i32, _i32]),
     ("gp_alg_bytes_per_node", C.c_double, [_vp]),
     ("gp_destroy", None, [_vp]),
+    ("gp_ensemble_max_nodes", _i64, [_i32, _i32]),
+    ("gp_ensemble_create", _i32, [C.POINTER(GpConfig), C.POINTER(C.c_uint64), _i64, C.POINTER(_vp)]),
+    ("gp_ensemble_step", _i64, [_vp, _i64]),
+    ("gp_ensemble_run", _i32, [_vp, C.POINTER(GpMember)]),
+    ("gp_ensemble_members", _i32, [_vp, C.POINTER(GpMember)]),
+    ("gp_ensemble_read_state", _i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    ("gp_ensemble_destroy", None, [_vp]),
 ]
 
 _libs = {}

@@ -42,6 +42,7 @@
 #include "gp_internal.hpp"
 #include "gp_full.hpp"
 #include "gp_fullbin.hpp"
+#include "gp_ensemble.hpp"
 
 namespace {
 // The experiments build (-DGP_EXPERIMENTS, libgossip_hip_exp.so) reads the GP_* environment
@@ -1908,6 +1909,12 @@ int create_common(const gp_config* cfg, int mode, int world, int rank, const uin
 }
 
 }  // namespace
+
+// For gp_ensemble_api.hip (declared in gp_ensemble.hpp): the same error slot and device check.
+namespace gp {
+void api_set_err(const char* msg) { g_err = msg; }
+int api_check_device(int device) { return check_device(device); }
+}  // namespace gp
 
 extern "C" {
 

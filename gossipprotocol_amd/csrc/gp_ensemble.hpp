@@ -1,0 +1,88 @@
+// gp_ensemble.hpp -- ensemble runs (gp_ensemble.hip): one workgroup simulates one
+// whole small network in LDS, a grid of workgroups runs many seeds at once.
+// This header is the LDS layout (and with it the population cap per pair) plus
+// the host launch interface; DESIGN.md §9.
+#pragma once
+
+#include <stdint.h>
+
+#include "../../include/gossip_hip.h"
+#include "gp_device.hpp"
+
+namespace gp {
+
+constexpr int ENS_THREADS = 1024;            // largest workgroup
+constexpr int ENS_NPT_MAX = 8;               // push-sum: node slots a thread keeps in registers
+constexpr uint32_t ENS_LDS_MAX = 150 * 1024; // dynamic LDS a member may ask for (a CU has 160 KiB)
+constexpr uint32_t ENS_LDS_HDR = 16;         // [0] cumulative alerts, [1] injector live count
+constexpr uint32_t ENS_NONE = 0xFFFFu;       // end of a receiver's message list (node ids are < 0xFFFF)
+
+constexpr uint32_t ens_up8(uint32_t b) { return (b + 7u) & ~7u; }
+
+// LDS image of one member, arrays in this order, each padded to 8 bytes:
+//   gossip   : c int32[P], inc int32[P], rnd u16[P] (Imp3D), live bitmap u32[ceil(T/32)] (not full)
+//   push-sum : hs f64[P], hw f64[P] (the halves a sender offers this round), head u32[P] + next u16[P]
+//              (full, Imp3D: per-receiver list of this round's random-edge senders), rnd u16[P] (Imp3D),
+//              dir u8[P] (not full)
+// The per-node (s, w, flags) of push-sum live in registers (ENS_NPT_MAX slots per thread).
+constexpr uint32_t ens_lds_bytes(int topo, int alg, uint32_t P) {
+    uint32_t b = ENS_LDS_HDR;
+    if (alg == GOSSIP) {
+        b += ens_up8(4 * P) * 2;
+        if (topo == IMP3D) b += ens_up8(2 * P);
+        if (topo != FULL) b += ens_up8(4 * ((P + 31) / 32));
+    } else {
+        b += 8 * P * 2;
+        if (topo == FULL || topo == IMP3D) b += ens_up8(4 * P) + ens_up8(2 * P);
+        if (topo == IMP3D) b += ens_up8(2 * P);
+        if (topo != FULL) b += ens_up8(P);
+    }
+    return b;
+}
+
+// Largest population a member may have: the LDS image fits and every node has a
+// thread slot.  A compile-time function of the layout above.
+constexpr uint32_t ens_max_population(int topo, int alg) {
+    uint32_t P = (uint32_t)ENS_THREADS * ENS_NPT_MAX;
+    while (P > 2 && ens_lds_bytes(topo, alg, P) > ENS_LDS_MAX) --P;
+    return P;
+}
+static_assert(ens_max_population(IMP3D, PUSHSUM) >= 1001 && ens_max_population(FULL, PUSHSUM) >= 1001, "report range");
+static_assert((uint32_t)ENS_THREADS * ENS_NPT_MAX < ENS_NONE, "node ids must fit the 16-bit list links");
+
+// Largest num_nodes: line / full P = n + 1; 3D / Imp3D the largest whole cube.
+constexpr int64_t ens_max_nodes(int topo, int alg) {
+    const uint32_t P = ens_max_population(topo, alg);
+    if (topo == LINE || topo == FULL) return (int64_t)P - 1;
+    uint32_t g = 1;
+    while ((g + 1) * (g + 1) * (g + 1) <= P) ++g;
+    return (int64_t)g * g * g;
+}
+
+// Kernel arguments.  rec[m] is member m's record (gp_member; `reserved` carries the
+// injector's live count between launches); idx[b] is the member workgroup b runs.
+struct EnsArgs {
+    gp_member* rec;
+    const uint32_t* idx;
+    int32_t* c;      // gossip: nseeds x P rumour counters
+    uint32_t* bits;  // gossip, not full: nseeds x nwords live bitmap of the injector
+    double* s;       // push-sum: nseeds x P
+    double* w;
+    uint8_t* fl;     // push-sum: nseeds x P, bit0 active, bit1 converged, bits2-3 count
+    Geom G;
+    uint32_t nwords;
+    int32_t init;        // 1: set the member up from its seed instead of loading it
+    int64_t nrounds;     // rounds this launch may run
+    int64_t max_rounds;  // cap on a member's total rounds
+};
+
+// Raises the kernel's dynamic-LDS limit for population P; once per handle.
+hipError_t ens_setup(int topo, int alg, uint32_t P);
+// Plain launch, one workgroup per listed member.
+hipError_t ens_launch(int topo, int alg, const EnsArgs& a, uint32_t nblocks, hipStream_t st);
+
+// gp_api.hip: the calling thread's gp_last_error() message and the gfx950 device check.
+void api_set_err(const char* msg);
+int api_check_device(int device);
+
+}  // namespace gp

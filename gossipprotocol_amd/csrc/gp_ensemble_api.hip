@@ -1,0 +1,321 @@
+// gp_ensemble_api.hip -- C-ABI of ensemble runs (include/gossip_hip.h, gp_ensemble_*):
+// argument checks, the members' stored state in HBM, and the launch loop that hands
+// the unfinished members to gp_ensemble.hip in chunks of rounds.  DESIGN.md §9.
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <new>
+#include <vector>
+
+#include "gp_ensemble.hpp"
+
+using namespace gp;
+
+namespace {
+
+// Rounds one launch may run.  Every kernel loop is bounded by its launch's round
+// count, and a launch should stay well under a second.  Measured on an MI355X
+// (DESIGN.md §9.4, 256 members): a round takes 0.5-4.4 us at n = 1000 and 2.2-40 us
+// at the population cap (8 node slots per thread; slowest: Imp3D push-sum, 5832
+// nodes), so 8192 rounds are 4-36 ms at n = 1000 and at most 0.33 s at the cap,
+// while the longest runs of the report's range (line push-sum, ~13000 rounds) still
+// take only two launches.  When there are more members than CUs (256; a CU holds at
+// least one workgroup), the workgroups run in waves, so the chunk shrinks by the
+// number of waves, down to a floor of 256 rounds, below which the launch overhead
+// (~10 us and the record copy) would show.
+constexpr int64_t ENS_LAUNCH_ROUNDS = 8192;
+constexpr int64_t ENS_LAUNCH_ROUNDS_MIN = 256;
+constexpr int64_t ENS_CUS = 256;
+
+int64_t launch_rounds(size_t members) {
+    const int64_t waves = ((int64_t)members + ENS_CUS - 1) / ENS_CUS;
+    return std::max(ENS_LAUNCH_ROUNDS_MIN, ENS_LAUNCH_ROUNDS / std::max<int64_t>(1, waves));
+}
+
+void set_err(const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    api_set_err(buf);
+}
+
+#define ENS_HIP_TRY(expr)                                                               \
+    do {                                                                                \
+        hipError_t e_ = (expr);                                                         \
+        if (e_ != hipSuccess) {                                                         \
+            set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+            return GP_EHIP;                                                             \
+        }                                                                               \
+    } while (0)
+
+bool pair_ok(int32_t topology, int32_t algorithm) {
+    if (topology < GP_LINE || topology > GP_IMP3D) {
+        set_err("unknown topology id %d", topology);
+        return false;
+    }
+    if (algorithm != GP_GOSSIP && algorithm != GP_PUSHSUM) {
+        set_err("unknown algorithm id %d", algorithm);
+        return false;
+    }
+    return true;
+}
+
+int64_t max_nodes(int topo, int alg) {
+    // ens_max_nodes is a compile-time function of the LDS layout: one constant per pair
+    static constexpr int64_t table[4][2] = {
+        {ens_max_nodes(LINE, GOSSIP), ens_max_nodes(LINE, PUSHSUM)},
+        {ens_max_nodes(FULL, GOSSIP), ens_max_nodes(FULL, PUSHSUM)},
+        {ens_max_nodes(GRID3D, GOSSIP), ens_max_nodes(GRID3D, PUSHSUM)},
+        {ens_max_nodes(IMP3D, GOSSIP), ens_max_nodes(IMP3D, PUSHSUM)},
+    };
+    return table[topo][alg];
+}
+
+}  // namespace
+
+struct gp_ensemble {
+    gp_config cfg{};
+    int64_t P = 0, T = 0, g = 0;
+    int64_t nseeds = 0;
+    uint32_t nwords = 0;
+    hipStream_t stream = nullptr;
+    EnsArgs args{};
+    uint32_t* d_idx = nullptr;
+    std::vector<void*> allocs;
+    std::vector<gp_member> rec;    // host copy of the member records, refreshed after every launch
+    std::vector<uint32_t> running; // unfinished members, in member order
+};
+
+namespace {
+
+template <typename T>
+int ens_alloc(gp_ensemble* e, T** p, size_t count) {
+    void* v = nullptr;
+    const size_t bytes = std::max<size_t>(16, count * sizeof(T));
+    const hipError_t err = hipMalloc(&v, bytes);
+    if (err != hipSuccess) {
+        set_err("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(err));
+        return GP_ENOMEM;
+    }
+    e->allocs.push_back(v);
+    *p = static_cast<T*>(v);
+    return GP_OK;
+}
+
+// One launch over the running members: up to nrounds rounds each (init: set them up
+// from their seeds instead).  Refreshes the records and the running list.
+int launch(gp_ensemble* e, int64_t nrounds, bool init) {
+    const size_t n = e->running.size();
+    ENS_HIP_TRY(hipMemcpyAsync(e->d_idx, e->running.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    e->args.nrounds = nrounds;
+    e->args.init = init ? 1 : 0;
+    ENS_HIP_TRY(ens_launch(e->cfg.topology, e->cfg.algorithm, e->args, (uint32_t)n, e->stream));
+    ENS_HIP_TRY(hipMemcpyAsync(e->rec.data(), e->args.rec, e->rec.size() * sizeof(gp_member), hipMemcpyDeviceToHost,
+                               e->stream));
+    ENS_HIP_TRY(hipStreamSynchronize(e->stream));
+    size_t keep = 0;
+    for (size_t q = 0; q < n; ++q)
+        if (e->rec[e->running[q]].status == GP_STATUS_RUNNING) e->running[keep++] = e->running[q];
+    e->running.resize(keep);
+    return GP_OK;
+}
+
+int create(gp_ensemble* e, const uint64_t* seeds) {
+    const int topo = e->cfg.topology, alg = e->cfg.algorithm;
+    const size_t n = (size_t)e->nseeds, P = (size_t)e->P;
+    ENS_HIP_TRY(hipSetDevice(e->cfg.device));
+    ENS_HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    ENS_HIP_TRY(ens_setup(topo, alg, (uint32_t)P));
+    EnsArgs& a = e->args;
+    int rc = ens_alloc(e, &a.rec, n);
+    if (!rc) rc = ens_alloc(e, &e->d_idx, n);
+    if (alg == GP_GOSSIP) {
+        if (!rc) rc = ens_alloc(e, &a.c, n * P);
+        if (!rc && topo != GP_FULL) rc = ens_alloc(e, &a.bits, n * e->nwords);
+    } else {
+        if (!rc) rc = ens_alloc(e, &a.s, n * P);
+        if (!rc) rc = ens_alloc(e, &a.w, n * P);
+        if (!rc) rc = ens_alloc(e, &a.fl, n * P);
+    }
+    if (rc) return rc;
+    a.idx = e->d_idx;
+    a.G = Geom{};
+    a.G.P = (uint32_t)e->P;
+    a.G.T = (uint32_t)e->T;
+    a.G.g = (uint32_t)e->g;
+    a.G.g2 = (uint32_t)(e->g * e->g);
+    a.G.div_g = make_fastdiv(a.G.g);
+    a.G.div_g2 = make_fastdiv(a.G.g2);
+    a.nwords = e->nwords;
+    a.max_rounds = e->cfg.max_rounds;
+    e->rec.assign(n, gp_member{});
+    e->running.resize(n);
+    for (size_t m = 0; m < n; ++m) {
+        e->rec[m].seed = seeds[m];
+        e->rec[m].status = GP_STATUS_RUNNING;
+        e->running[m] = (uint32_t)m;
+    }
+    ENS_HIP_TRY(hipMemcpyAsync(a.rec, e->rec.data(), n * sizeof(gp_member), hipMemcpyHostToDevice, e->stream));
+    return launch(e, 0, true);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t gp_ensemble_max_nodes(int32_t topology, int32_t algorithm) {
+    if (!pair_ok(topology, algorithm)) return GP_EINVAL;
+    return max_nodes(topology, algorithm);
+}
+
+int gp_ensemble_create(const gp_config* cfg, const uint64_t* seeds, int64_t nseeds, gp_ensemble** out) {
+    if (!cfg || !out) {
+        set_err("gp_ensemble_create: null argument");
+        return GP_EINVAL;
+    }
+    *out = nullptr;
+    if (!seeds) {
+        set_err("gp_ensemble_create: seeds is null");
+        return GP_EINVAL;
+    }
+    if (nseeds <= 0 || nseeds > 0x7FFFFFFFll) {
+        set_err("gp_ensemble_create: nseeds must be in [1, 2^31) (got %lld)", (long long)nseeds);
+        return GP_EINVAL;
+    }
+    if (cfg->num_gpus != 1 || (cfg->flags & GP_FLAG_VIRTUAL_RANKS)) {
+        set_err("gp_ensemble_create: an ensemble runs on one GPU (num_gpus = %d, flags = %d)", cfg->num_gpus, cfg->flags);
+        return GP_EINVAL;
+    }
+    if (cfg->max_rounds <= 0) {
+        set_err("gp_ensemble_create: max_rounds must be > 0 (an ensemble needs an explicit cap)");
+        return GP_EINVAL;
+    }
+    if (!pair_ok(cfg->topology, cfg->algorithm)) return GP_EINVAL;
+    int64_t P = 0, T = 0, g = 0;
+    if (gp_resolve(cfg->num_nodes, cfg->topology, &P, &T, &g)) return GP_EINVAL;
+    if (P < 2) {
+        set_err("gp_ensemble_create: a population of %lld has no edge", (long long)P);
+        return GP_EINVAL;
+    }
+    const int64_t cap = max_nodes(cfg->topology, cfg->algorithm);
+    if (cfg->num_nodes > cap) {
+        set_err("gp_ensemble_create: num_nodes %lld exceeds the ensemble cap %lld of this pair (one workgroup's LDS); "
+                "use gp_create", (long long)cfg->num_nodes, (long long)cap);
+        return GP_EINVAL;
+    }
+    const int rc_dev = api_check_device(cfg->device);
+    if (rc_dev) return rc_dev;
+
+    gp_ensemble* e = new (std::nothrow) gp_ensemble();
+    if (!e) {
+        set_err("out of host memory");
+        return GP_ENOMEM;
+    }
+    e->cfg = *cfg;
+    e->P = P;
+    e->T = T;
+    e->g = g;
+    e->nseeds = nseeds;
+    e->nwords = (uint32_t)((T + 31) / 32);
+    const int rc = create(e, seeds);
+    if (rc) {
+        gp_ensemble_destroy(e);  // (hipFree does not touch the error message)
+        return rc;
+    }
+    *out = e;
+    return GP_OK;
+}
+
+int64_t gp_ensemble_step(gp_ensemble* e, int64_t nrounds) {
+    if (!e || nrounds < 0) {
+        set_err("gp_ensemble_step: bad argument");
+        return GP_EINVAL;
+    }
+    ENS_HIP_TRY(hipSetDevice(e->cfg.device));
+    while (nrounds > 0 && !e->running.empty()) {
+        const int64_t chunk = std::min(nrounds, launch_rounds(e->running.size()));
+        const int rc = launch(e, chunk, false);
+        if (rc) return rc;
+        nrounds -= chunk;
+    }
+    return (int64_t)e->running.size();
+}
+
+int gp_ensemble_members(gp_ensemble* e, gp_member* out) {
+    if (!e || !out) {
+        set_err("gp_ensemble_members: null argument");
+        return GP_EINVAL;
+    }
+    for (int64_t m = 0; m < e->nseeds; ++m) {
+        out[m] = e->rec[(size_t)m];
+        out[m].reserved = 0;
+    }
+    return GP_OK;
+}
+
+int gp_ensemble_run(gp_ensemble* e, gp_member* out) {
+    if (!e) {
+        set_err("gp_ensemble_run: null handle");
+        return GP_EINVAL;
+    }
+    // every member stops at max_rounds (> 0) at the latest
+    while (!e->running.empty()) {
+        const int64_t left = gp_ensemble_step(e, ENS_LAUNCH_ROUNDS);
+        if (left < 0) return (int)left;
+    }
+    return out ? gp_ensemble_members(e, out) : GP_OK;
+}
+
+int gp_ensemble_read_state(gp_ensemble* e, int64_t member, int64_t first, int64_t count, int32_t* c, double* s,
+                           double* w, uint8_t* flags) {
+    if (!e) {
+        set_err("gp_ensemble_read_state: null handle");
+        return GP_EINVAL;
+    }
+    if (member < 0 || member >= e->nseeds || first < 0 || count < 0 || first + count > e->P) {
+        set_err("gp_ensemble_read_state: member %lld range [%lld, %lld) outside %lld members of %lld nodes",
+                (long long)member, (long long)first, (long long)(first + count), (long long)e->nseeds, (long long)e->P);
+        return GP_EINVAL;
+    }
+    if (count == 0) return GP_OK;
+    ENS_HIP_TRY(hipSetDevice(e->cfg.device));
+    const size_t at = (size_t)member * (size_t)e->P + (size_t)first, n = (size_t)count;
+    if (e->cfg.algorithm == GP_GOSSIP) {
+        std::vector<int32_t> hc(n);
+        ENS_HIP_TRY(hipMemcpyAsync(hc.data(), e->args.c + at, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        ENS_HIP_TRY(hipStreamSynchronize(e->stream));
+        const int64_t seed_node = e->rec[(size_t)member].seed_node;
+        for (size_t q = 0; q < n; ++q) {
+            const int32_t ci = hc[q];
+            if (c) c[q] = ci;
+            if (s) s[q] = 0.0;
+            if (w) w[q] = 0.0;
+            if (flags) {
+                const int act = ((int64_t)(first + (int64_t)q) == seed_node || ci >= 1) && ci <= 10;
+                flags[q] = (uint8_t)(act | ((ci >= (int32_t)GOSSIP_DONE) << 1));
+            }
+        }
+    } else {
+        if (s) ENS_HIP_TRY(hipMemcpyAsync(s, e->args.s + at, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        if (w) ENS_HIP_TRY(hipMemcpyAsync(w, e->args.w + at, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        if (flags) ENS_HIP_TRY(hipMemcpyAsync(flags, e->args.fl + at, n, hipMemcpyDeviceToHost, e->stream));
+        ENS_HIP_TRY(hipStreamSynchronize(e->stream));
+        if (c) std::fill(c, c + n, 0);
+    }
+    return GP_OK;
+}
+
+void gp_ensemble_destroy(gp_ensemble* e) {
+    if (!e) return;
+    (void)hipSetDevice(e->cfg.device);
+    if (e->stream) {
+        (void)hipStreamSynchronize(e->stream);
+        (void)hipStreamDestroy(e->stream);
+    }
+    for (void* p : e->allocs) (void)hipFree(p);
+    delete e;
+}
+
+}  // extern "C"

@@ -177,6 +177,79 @@ class Simulation:
         return self._L.gp_alg_bytes_per_node(self._h)
 
 
+def ensemble_max_nodes(topology: str, algorithm: str) -> int:
+    """Largest num_nodes an :class:`Ensemble` accepts for the pair (host only)."""
+    return L.check(L.lib().gp_ensemble_max_nodes(parse_topology(topology), parse_algorithm(algorithm)))
+
+
+class Ensemble:
+    """Many small networks at once on one MI355X, one per seed (handle over
+    gp_ensemble): the regime of the reference's published curves, n = 100..1000
+    (README.md, Report.pdf).  Each member is one workgroup with its state in LDS and
+    is bit-identical to ``Simulation(num_nodes, topology, algorithm, seed)``."""
+
+    def __init__(self, num_nodes: int, topology: str, algorithm: str, seeds, max_rounds: int, device: int = 0):
+        self._L = L.lib()
+        self.seeds = [int(s) for s in seeds]
+        cfg = L.GpConfig()
+        cfg.num_nodes = num_nodes
+        cfg.topology = parse_topology(topology)
+        cfg.algorithm = parse_algorithm(algorithm)
+        cfg.num_gpus = 1
+        cfg.device = device
+        cfg.max_rounds = max_rounds
+        self.topology, self.algorithm = topology, algorithm
+        self.population = resolve(num_nodes, topology)[0]
+        arr = (C.c_uint64 * max(1, len(self.seeds)))(*self.seeds)
+        h = C.c_void_p()
+        L.check(self._L.gp_ensemble_create(C.byref(cfg), arr, len(self.seeds), C.byref(h)), self._L)
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gp_ensemble_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def __len__(self):
+        return len(self.seeds)
+
+    def step(self, nrounds: int) -> int:
+        """Every unfinished member runs up to nrounds more rounds; returns how many still run."""
+        return L.check(self._L.gp_ensemble_step(self._h, nrounds), self._L)
+
+    def run(self):
+        """Run every member to convergence (or max_rounds); returns the member records."""
+        out = (L.GpMember * len(self.seeds))()
+        L.check(self._L.gp_ensemble_run(self._h, out), self._L)
+        return list(out)
+
+    def members(self):
+        """The member records (GpMember: seed, rounds, converged, seed_node, status), in seed order."""
+        out = (L.GpMember * len(self.seeds))()
+        L.check(self._L.gp_ensemble_members(self._h, out), self._L)
+        return list(out)
+
+    def state(self, member: int, first: int = 0, count: int | None = None):
+        """Node state of one member, as :meth:`Simulation.state`."""
+        count = self.population - first if count is None else count
+        c = np.zeros(count, np.int32)
+        s = np.zeros(count, np.float64)
+        w = np.zeros(count, np.float64)
+        f = np.zeros(count, np.uint8)
+        L.check(self._L.gp_ensemble_read_state(self._h, member, first, count, c.ctypes.data, s.ctypes.data,
+                                               w.ctypes.data, f.ctypes.data), self._L)
+        return {"c": c, "s": s, "w": w, "flags": f}
+
+
 def run(num_nodes: int, topology: str, algorithm: str, seed: int = 1, max_rounds: int = 0, device: int = 0):
     """`dotnet run num_nodes topology algorithm` as a function: returns the gp_result."""
     with Simulation(num_nodes, topology, algorithm, seed=seed, max_rounds=max_rounds, device=device) as sim:

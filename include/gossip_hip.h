@@ -170,6 +170,40 @@ double gp_alg_bytes_per_node(gp_sim* sim);
 
 void gp_destroy(gp_sim* sim);
 
+/* ---- Ensembles: many small networks per launch ----------------
+ * The reference was run at 100..1000 nodes (README.md, Report.pdf), where what
+ * is wanted is statistics over many seeds.  An ensemble simulates one network
+ * per seed, each by one workgroup with its whole state in LDS, all seeds
+ * concurrently; every member is bit-identical to a gp_create / gp_run of the
+ * same (num_nodes, topology, algorithm, seed). */
+typedef struct gp_ensemble gp_ensemble;
+typedef struct gp_member {      /* one per seed, blittable */
+    uint64_t seed;
+    int64_t rounds;             /* rounds this member executed */
+    int64_t converged;          /* cumulative alerts */
+    int64_t seed_node;          /* `choice` (Program.fs:193,221,263) */
+    int32_t status;             /* GP_STATUS_* */
+    int32_t reserved;
+} gp_member;
+
+/* Largest num_nodes an ensemble accepts for the pair (host only, no GPU), or GP_EINVAL. */
+int64_t gp_ensemble_max_nodes(int32_t topology, int32_t algorithm);
+/* One member per seed, in the order of `seeds` (duplicates allowed).  cfg->seed is
+ * ignored; cfg->device and cfg->max_rounds are honoured, and max_rounds must be > 0.
+ * num_gpus must be 1 and num_nodes <= gp_ensemble_max_nodes(). */
+int gp_ensemble_create(const gp_config* cfg, const uint64_t* seeds, int64_t nseeds, gp_ensemble** out);
+/* Every unfinished member runs up to nrounds more rounds (stops after its converging
+ * round or at max_rounds).  Returns the members still running, or a GP_E* code. */
+int64_t gp_ensemble_step(gp_ensemble* e, int64_t nrounds);
+/* Runs until every member has converged or hit max_rounds; out (nseeds, may be NULL). */
+int gp_ensemble_run(gp_ensemble* e, gp_member* out);
+/* Copies the nseeds member records to out. */
+int gp_ensemble_members(gp_ensemble* e, gp_member* out);
+/* gp_read_state of one member. */
+int gp_ensemble_read_state(gp_ensemble* e, int64_t member, int64_t first, int64_t count, int32_t* c,
+                           double* s, double* w, uint8_t* flags);
+void gp_ensemble_destroy(gp_ensemble* e);
+
 #ifdef __cplusplus
 }
 #endif
