@@ -81,8 +81,4 @@ hipError_t ens_setup(int topo, int alg, uint32_t P);
 // Plain launch, one workgroup per listed member.
 hipError_t ens_launch(int topo, int alg, const EnsArgs& a, uint32_t nblocks, hipStream_t st);
 
-// gp_api.hip: the calling thread's gp_last_error() message and the gfx950 device check.
-void api_set_err(const char* msg);
-int api_check_device(int device);
-
 }  // namespace gp

@@ -1,15 +1,10 @@
 // gp_ensemble_api.hip -- C-ABI of ensemble runs (include/gossip_hip.h, gp_ensemble_*):
 // argument checks, the members' stored state in HBM, and the launch loop that hands
 // the unfinished members to gp_ensemble.hip in chunks of rounds.  DESIGN.md §9.
-#include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <new>
-#include <vector>
 
+#include "gp_host.hpp"
 #include "gp_ensemble.hpp"
-
-using namespace gp;
 
 namespace {
 
@@ -31,24 +26,6 @@ int64_t launch_rounds(size_t members) {
     const int64_t waves = ((int64_t)members + ENS_CUS - 1) / ENS_CUS;
     return std::max(ENS_LAUNCH_ROUNDS_MIN, ENS_LAUNCH_ROUNDS / std::max<int64_t>(1, waves));
 }
-
-void set_err(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    api_set_err(buf);
-}
-
-#define ENS_HIP_TRY(expr)                                                               \
-    do {                                                                                \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess) {                                                         \
-            set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return GP_EHIP;                                                             \
-        }                                                                               \
-    } while (0)
 
 bool pair_ok(int32_t topology, int32_t algorithm) {
     if (topology < GP_LINE || topology > GP_IMP3D) {
@@ -108,13 +85,13 @@ int ens_alloc(gp_ensemble* e, T** p, size_t count) {
 // from their seeds instead).  Refreshes the records and the running list.
 int launch(gp_ensemble* e, int64_t nrounds, bool init) {
     const size_t n = e->running.size();
-    ENS_HIP_TRY(hipMemcpyAsync(e->d_idx, e->running.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_idx, e->running.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     e->args.nrounds = nrounds;
     e->args.init = init ? 1 : 0;
-    ENS_HIP_TRY(ens_launch(e->cfg.topology, e->cfg.algorithm, e->args, (uint32_t)n, e->stream));
-    ENS_HIP_TRY(hipMemcpyAsync(e->rec.data(), e->args.rec, e->rec.size() * sizeof(gp_member), hipMemcpyDeviceToHost,
+    HIP_TRY(ens_launch(e->cfg.topology, e->cfg.algorithm, e->args, (uint32_t)n, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->rec.data(), e->args.rec, e->rec.size() * sizeof(gp_member), hipMemcpyDeviceToHost,
                                e->stream));
-    ENS_HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     size_t keep = 0;
     for (size_t q = 0; q < n; ++q)
         if (e->rec[e->running[q]].status == GP_STATUS_RUNNING) e->running[keep++] = e->running[q];
@@ -125,9 +102,9 @@ int launch(gp_ensemble* e, int64_t nrounds, bool init) {
 int create(gp_ensemble* e, const uint64_t* seeds) {
     const int topo = e->cfg.topology, alg = e->cfg.algorithm;
     const size_t n = (size_t)e->nseeds, P = (size_t)e->P;
-    ENS_HIP_TRY(hipSetDevice(e->cfg.device));
-    ENS_HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    ENS_HIP_TRY(ens_setup(topo, alg, (uint32_t)P));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    HIP_TRY(ens_setup(topo, alg, (uint32_t)P));
     EnsArgs& a = e->args;
     int rc = ens_alloc(e, &a.rec, n);
     if (!rc) rc = ens_alloc(e, &e->d_idx, n);
@@ -157,7 +134,7 @@ int create(gp_ensemble* e, const uint64_t* seeds) {
         e->rec[m].status = GP_STATUS_RUNNING;
         e->running[m] = (uint32_t)m;
     }
-    ENS_HIP_TRY(hipMemcpyAsync(a.rec, e->rec.data(), n * sizeof(gp_member), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(a.rec, e->rec.data(), n * sizeof(gp_member), hipMemcpyHostToDevice, e->stream));
     return launch(e, 0, true);
 }
 
@@ -205,7 +182,7 @@ int gp_ensemble_create(const gp_config* cfg, const uint64_t* seeds, int64_t nsee
                 "use gp_create", (long long)cfg->num_nodes, (long long)cap);
         return GP_EINVAL;
     }
-    const int rc_dev = api_check_device(cfg->device);
+    const int rc_dev = check_device(cfg->device);
     if (rc_dev) return rc_dev;
 
     gp_ensemble* e = new (std::nothrow) gp_ensemble();
@@ -233,7 +210,7 @@ int64_t gp_ensemble_step(gp_ensemble* e, int64_t nrounds) {
         set_err("gp_ensemble_step: bad argument");
         return GP_EINVAL;
     }
-    ENS_HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipSetDevice(e->cfg.device));
     while (nrounds > 0 && !e->running.empty()) {
         const int64_t chunk = std::min(nrounds, launch_rounds(e->running.size()));
         const int rc = launch(e, chunk, false);
@@ -280,12 +257,12 @@ int gp_ensemble_read_state(gp_ensemble* e, int64_t member, int64_t first, int64_
         return GP_EINVAL;
     }
     if (count == 0) return GP_OK;
-    ENS_HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipSetDevice(e->cfg.device));
     const size_t at = (size_t)member * (size_t)e->P + (size_t)first, n = (size_t)count;
     if (e->cfg.algorithm == GP_GOSSIP) {
         std::vector<int32_t> hc(n);
-        ENS_HIP_TRY(hipMemcpyAsync(hc.data(), e->args.c + at, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-        ENS_HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipMemcpyAsync(hc.data(), e->args.c + at, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
         const int64_t seed_node = e->rec[(size_t)member].seed_node;
         for (size_t q = 0; q < n; ++q) {
             const int32_t ci = hc[q];
@@ -298,10 +275,10 @@ int gp_ensemble_read_state(gp_ensemble* e, int64_t member, int64_t first, int64_
             }
         }
     } else {
-        if (s) ENS_HIP_TRY(hipMemcpyAsync(s, e->args.s + at, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        if (w) ENS_HIP_TRY(hipMemcpyAsync(w, e->args.w + at, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        if (flags) ENS_HIP_TRY(hipMemcpyAsync(flags, e->args.fl + at, n, hipMemcpyDeviceToHost, e->stream));
-        ENS_HIP_TRY(hipStreamSynchronize(e->stream));
+        if (s) HIP_TRY(hipMemcpyAsync(s, e->args.s + at, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        if (w) HIP_TRY(hipMemcpyAsync(w, e->args.w + at, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        if (flags) HIP_TRY(hipMemcpyAsync(flags, e->args.fl + at, n, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
         if (c) std::fill(c, c + n, 0);
     }
     return GP_OK;

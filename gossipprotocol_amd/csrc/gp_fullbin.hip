@@ -406,7 +406,7 @@ __global__ __launch_bounds__(FBR_THREADS, 1) void k_fb_split(FullBinArgs a, uint
 }
 
 // ---------------------------------------------------------------- several ranks
-// Contiguous id slabs (gp_api.hip make_bounds); W <= XMAXW.  Every rank's coarse bins
+// Contiguous id slabs (gp_setup.hip make_bounds); W <= XMAXW.  Every rank's coarse bins
 // have the size 2^s1 (full_bin_multi_s1), so a message to target t has the LDS key
 // kb(b) + ((t - bounds[b]) >> s1), b = owner of t, kb(b) = the bins of the ranks below b:
 // key order = destination rank, then the destination's coarse bin.

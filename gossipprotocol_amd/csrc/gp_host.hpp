@@ -1,0 +1,222 @@
+// gp_host.hpp -- what the host units of libgossip_hip.so share: gp_setup.hip (before round 0),
+// gp_exchange.hip (one round across ranks), gp_api.hip (C ABI, gp_step batch loop) and, for the
+// error slot and device check, gp_ensemble_api.hip.  Hidden symbols: not the library's surface.
+#pragma once
+#include <algorithm>
+#include <array>
+#include <chrono>
+#include <cmath>
+#include <cerrno>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <rccl/rccl.h>
+
+#include "../../include/gossip_hip.h"
+#include "gp_internal.hpp"
+#include "gp_full.hpp"
+#include "gp_fullbin.hpp"
+
+namespace {
+// The experiments build (-DGP_EXPERIMENTS, libgossip_hip_exp.so) reads the GP_* environment
+// overrides the kernel-variant tests use; the product library reads none (nullptr: every
+// override below folds away, its name included -- tests/test_abi.py checks the strings).
+inline const char* exp_env(const char* name) {
+#ifdef GP_EXPERIMENTS
+    return std::getenv(name);
+#else
+    (void)name;
+    return nullptr;
+#endif
+}
+}  // namespace
+#include "gp_xchg.hpp"
+
+using namespace gp;
+#pragma GCC visibility push(hidden)
+
+// The calling thread's gp_last_error() message: one slot per thread for all units (gp_api.hip).
+extern thread_local std::string g_err;
+void set_err(const char* fmt, ...);
+int check_device(int device);
+
+#define HIP_TRY(expr)                                                                   \
+    do {                                                                                \
+        hipError_t e_ = (expr);                                                         \
+        if (e_ != hipSuccess) {                                                         \
+            set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+            return GP_EHIP;                                                             \
+        }                                                                               \
+    } while (0)
+
+#define NCCL_TRY(expr)                                                                  \
+    do {                                                                                \
+        ncclResult_t r_ = (expr);                                                       \
+        if (r_ != ncclSuccess) {                                                        \
+            set_err("%s failed: %s (%s:%d)", #expr, ncclGetErrorString(r_), __FILE__, __LINE__); \
+            return GP_ENCCL;                                                            \
+        }                                                                               \
+    } while (0)
+
+constexpr int64_t BATCH = 1024;  // rounds queued per host synchronisation (<= HIST)
+static_assert(BATCH <= HIST, "alert ring must cover a batch");
+
+enum Mode { MODE_SINGLE = 0, MODE_VIRTUAL = 1, MODE_RCCL = 2 };
+
+// One inter-rank transfer of a slab: `bytes` at `ptr`, sent to or received from rank `peer`
+// (build_transfers / run_transfers, gp_exchange.hip).
+struct Xfer { bool send; int peer; uint8_t* ptr; size_t bytes; };
+
+// One rank's share of the network.
+struct Slab {
+    DevState S{};
+    int rank = 0;
+    uint32_t hi = 0;  // one past the last owned id
+    // Imp3D random-edge exchange (W > 1)
+    uint32_t* pos = nullptr;
+    uint8_t* xdst = nullptr;  // owner rank of each local sender's random-edge target (k_pack)
+    uint8_t* xsend = nullptr;
+    uint8_t* xrecv = nullptr;
+    uint32_t nedges = 0;
+    std::vector<uint32_t> cap_out, cap_in;           // [h * W + b]: region h of the buffer to / from rank b
+    std::vector<size_t> soff, sbytes, roff, rbytes;
+    unsigned int* overflow = nullptr;  // device flag
+    // Imp3D push-sum over several ranks: sender-ordered lists (gp_xchg.hpp)
+    bool lists = false;
+    uint32_t nt = 0;                   // the slab's tiles
+    uint32_t tb[XMAXH + 1] = {};       // region h: tiles [tb[h], tb[h + 1])
+    uint32_t* gw = nullptr;            // [tile * W + d]: first header word of the tile's segment
+    uint16_t* xdr = nullptr;           // [id - lo]: d << 10 | rank in the tile's list for d (static)
+    uint8_t* lwt = nullptr;            // [tile * (W + 1) + d]: the tile's LDS word layout in k_list_pack
+    uint32_t* xcnt = nullptr;          // [h * W + d]: reservation counters of the send chunks
+    std::vector<size_t> lhdr, lval;    // send buffer: byte offsets of chunk (h, d)'s header words / slots
+    std::vector<size_t> rhdr, rval;    // receive buffer: byte offsets of chunk (h, p)'s header words / slots
+    size_t xr_stride = 0;              // the receive buffer of odd rounds at xrecv + xr_stride (region-by-region
+                                       // rounds: the next round's lists arrive during this one), else 0
+    std::vector<uint32_t> vbase;       // [h * W + d]: index of my chunk's first slot in d's vals region
+    // full push-sum over several ranks: this rank's own share of region h's bins, by round parity:
+    // parity 0 in xrecv (its receive region from itself), parity 1 in xown -- the fold of round r
+    // fills parity r + 1 while the split of round r has read parity r, and a round's counters are
+    // all cleared at its start (launch_round_full_multi)
+    uint8_t* xown = nullptr;
+    size_t ooff[FB_REGIONS] = {};
+    // Imp3D gossip (column kernel) over several ranks: random-edge sends as bitmaps (gp_xchg.hpp)
+    bool bits = false;
+    uint32_t* rbits_in = nullptr;      // receive bitmap: source a's chunk at bit ro[a]
+    uint32_t* tgt = nullptr;           // local target of every receive-bitmap bit
+    uint32_t nbits_out = 0, nbits_in = 0;  // bitmap sizes (multiples of BITS_ALIGN)
+    std::vector<uint32_t> bo, bn, ro, rn;  // [peer]: chunk bit offset / bits, send and receive side
+    // push-sum halo planes (3D / Imp3D, W > 1): the senders' (s, w) toward each neighbour, compacted
+    // ([0]: lower neighbour, [1]: upper; k_halo_pack / k_halo_expand, gp_xchg.hpp)
+    double2* hsend[2] = {nullptr, nullptr};
+    double2* hrecv[2] = {nullptr, nullptr};
+    // every transfer of a round, by the parity of the round it prepares (build_transfers): the
+    // halo planes, and region h's random-edge / full-topology messages
+    std::vector<Xfer> xhalo[2];
+    std::vector<std::vector<Xfer>> xplan[2];  // [parity][h]
+};
+
+// (the C ABI's handle type: default visibility, like its declaration in include/gossip_hip.h)
+#pragma GCC visibility pop
+struct gp_sim {
+    gp_config cfg{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int grid = 1;
+    int cus = 1;  // compute units of the device
+    int64_t P = 0, T = 0, g = 0;
+    int mode = MODE_SINGLE;
+    int world = 1, rank = 0;  // ranks sharing the population; this process's rank (RCCL)
+    std::vector<uint32_t> bounds;  // world + 1 slab boundaries (global ids)
+    uint32_t halo = 0;             // ids per halo side
+    std::vector<Slab> slab;        // MODE_VIRTUAL: all ranks; otherwise this rank's
+    ncclComm_t comm = nullptr;
+    int64_t rounds_done = 0;
+    int64_t alerts_total = 0;
+    bool done = false;
+    Ctl* host_ctl = nullptr;  // pinned mirror of slab 0's control block (global bookkeeping)
+    std::vector<void*> allocs;
+    // kernel timing
+    bool timing = false;
+    std::vector<hipEvent_t> ev;
+    double kernel_ms = 0.0;
+    int64_t launches = 0;
+    // exchange buffers per rank pair: xhalves regions (2: full-topology push-sum, whose exchange runs
+    // in two halves of each rank's senders on xstream, overlapped with the send / coarse passes)
+    int xhalves = 1;
+    size_t halo_slots = 0;  // push-sum halo planes travel compacted (setup_halo): slots per buffer, else 0
+    uint32_t halo_cap = 0;  // ... slots per 1024-node chunk (halo_chunk_cap)
+    // Imp3D push-sum lists: header words of chunk (h, a -> b) at [(a * xhalves + h) * world + b],
+    // every slab's (each rank computes the whole table from the global random edges)
+    std::vector<uint32_t> list_nw;
+    hipStream_t xstream = nullptr;
+    hipEvent_t ev_send[XMAXH] = {}, ev_xfer[XMAXH] = {};
+    BlockPlan bplan{};  // KERNEL_BLOCK
+};
+#pragma GCC visibility push(hidden)
+
+inline int dev_alloc(gp_sim* s, void** p, size_t bytes) {
+    if (bytes == 0) bytes = 16;
+    hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) {
+        set_err("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        return GP_ENOMEM;
+    }
+    s->allocs.push_back(*p);
+    return GP_OK;
+}
+
+template <typename T>
+int dev_alloc_t(gp_sim* s, T** p, size_t count) {
+    void* v = nullptr;
+    int rc = dev_alloc(s, &v, count * sizeof(T));
+    *p = static_cast<T*>(v);
+    return rc;
+}
+
+// Setup temporaries: freed when the scope ends, on success and on every error return.
+struct Scratch {
+    std::vector<void*> ptrs;
+    template <typename T>
+    hipError_t alloc(T** p, size_t count) {
+        void* v = nullptr;
+        const hipError_t e = hipMalloc(&v, count * sizeof(T));
+        if (e == hipSuccess) ptrs.push_back(v);
+        *p = static_cast<T*>(v);
+        return e;
+    }
+    ~Scratch() {
+        for (void* v : ptrs) (void)hipFree(v);
+    }
+};
+
+// Imp3D gossip on the column kernel: random-edge deliveries are counted by their
+// senders (rq) and cross ranks as counts; no bitmap, in-edge tags or slots.
+inline bool col_gossip_counts(const DevState& S) { return S.topo == IMP3D && S.alg == GOSSIP && S.kernel == KERNEL_COL; }
+
+// Coarse bins of rank p's receivers, 2^s1 each (full push-sum over several ranks, FbBins).
+inline uint32_t full_coarse_bins(const std::vector<uint32_t>& bounds, int p, uint32_t s1) {
+    return (uint32_t)(((uint64_t)bounds[p + 1] - bounds[p] + (1ull << s1) - 1) >> s1);
+}
+
+// gp_setup.hip
+void full_region(uint32_t nloc, int NH, int h, uint32_t& t0, uint32_t& t1, uint32_t& s0, uint32_t& s1);
+void xregion(const Slab& sl, int NH, int h, uint32_t& s_lo, uint32_t& s_hi);
+int create_common(const gp_config* cfg, int mode, int world, int rank, const uint8_t* uid, gp_sim** out);
+
+// gp_exchange.hip
+void build_transfers(gp_sim* s);
+int exchange(gp_sim* s, uint32_t rn);
+int finalize(gp_sim* s, uint32_t round_done, uint32_t round_next);
+uint32_t round_launches(const gp_sim* s);
+int launch_round(gp_sim* s, uint32_t r, hipEvent_t* ev);
+#pragma GCC visibility pop

@@ -256,7 +256,7 @@ struct DevState {
     uint32_t* tq;
     // walk 3: the slab's tiles (relative to lo / TILE) in visiting order, XCD c's
     // items at [woff[0][c], woff[0][c + 1]); with rregions > 1 launches per round
-    // (launch_round_regions, gp_api.hip) launch h visits region h's tiles, XCD c's
+    // (launch_round_regions, gp_exchange.hip) launch h visits region h's tiles, XCD c's
     // at [woff[h][c], woff[h][c + 1])
     uint32_t* wtiles;
     uint32_t rregions;

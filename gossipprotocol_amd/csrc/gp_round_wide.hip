@@ -7,7 +7,7 @@
 // the network has only a few tiles per resident block: C2 (3D push-sum, P = 10^6,
 // 977 tiles) measured 26.4 -> 21.0 us per round (profiles/r04/c2_tile_shape.txt).
 // At 10^9 nodes the 4-nodes-per-thread kernel is faster (more waves' worth of
-// memory-level parallelism per VGPR), so gp_api.hip's choose_kernel picks by size.
+// memory-level parallelism per VGPR), so gp_setup.hip's choose_kernel picks by size.
 #define GP_ROUND_WIDE 1
 #define GP_TPB 1024
 #define GP_NPT 1

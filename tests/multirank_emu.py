@@ -2,13 +2,13 @@
 
 TEST INFRASTRUCTURE ONLY (tests/test_multirank_gloo.py).  Each torch.distributed
 (gloo) rank owns the slab of node ids the library would give it
-(gp_api.hip make_bounds: whole x-planes for 3D / Imp3D, contiguous ids for
+(gp_setup.hip make_bounds: whole x-planes for 3D / Imp3D, contiguous ids for
 line) and runs SRS v1 rounds for its slab with numpy, talking to the other
 ranks only through the library's exchange plan:
 
   * halo refresh: after every round the boundary plane (line: node) of node
     bytes -- here the direction / active fields -- and (s, w) goes to the
-    neighbouring rank (gp_api.hip exchange, halo part);
+    neighbouring rank (gp_exchange.hip exchange, halo part);
   * random-edge messages: every sender whose next direction is its random edge
     and whose target lives on another rank sends.  Push-sum: sender-ordered lists
     (ListPlan; gp_xchg.hpp k_list_pack) -- per region and destination one header
@@ -125,7 +125,7 @@ class Geometry:
 
 
 def slab_bounds(P, g, topo, W):
-    """gp_api.hip make_bounds."""
+    """gp_setup.hip make_bounds."""
     if topo == "line":
         return [P * w // W for w in range(W + 1)], 1
     if topo == "full":
@@ -154,9 +154,9 @@ def region_tiles(lo, nloc, g2, NH, nt):
 
 class ListPlan:
     """Imp3D push-sum over several ranks: the sender-ordered lists (gp_xchg.hpp,
-    gp_api.hip build_lists / setup_exchange).  List L_ab = slab a's senders whose
+    gp_setup.hip build_lists / setup_exchange).  List L_ab = slab a's senders whose
     random edge lands on slab b, in id order, cut into the slab's tiles and NH
-    regions of consecutive tiles (region_tiles: whole planes, gp_api.hip XREGIONS = 4);
+    regions of consecutive tiles (region_tiles: whole planes, gp_setup.hip XREGIONS = 4);
     every (tile, b) segment starts on a 64-entry
     boundary.  Computed from the global random edges, like every rank of the
     library does for every slab."""
@@ -235,7 +235,7 @@ class ListPlan:
 
 
 def full_capacity(na, nb, P):
-    """Per-pair message capacity of the full-topology exchange (gp_api.hip
+    """Per-pair message capacity of the full-topology exchange (gp_setup.hip
     setup_exchange): messages a -> b are at most Binomial(na, nb / (P - 1))."""
     m = na * nb / (P - 1)
     return int(min(np.ceil(m + 12.0 * np.sqrt(m) + 64.0), na))
@@ -265,7 +265,7 @@ def full_bin_multi_cap(n, s1, P):
 
 
 def full_region(n, NH, h):
-    """Region h of NH of a slab of n ids (gp_api.hip full_region): fine tiles [t0, t1),
+    """Region h of NH of a slab of n ids (gp_setup.hip full_region): fine tiles [t0, t1),
     local sender ids [s0, s1)."""
     nt = -(-n // (1 << FB_TB))
     t0, t1 = nt * h // NH, nt * (h + 1) // NH
@@ -610,7 +610,7 @@ class RankSim:
 
     def _full_pushsum_exchange(self, snd, t, payload):
         """Push-sum messages -> this rank's receivers (gp_fullbin.hip several ranks,
-        gp_api.hip launch_round_full_multi, round 6): the senders of each of the slab's two
+        gp_exchange.hip launch_round_full_multi, round 6): the senders of each of the slab's two
         exchange regions (whole fine tiles, full_region) are binned by destination rank and
         the destination's coarse bin (2^s1 receivers, the same size on every rank) in
         arbitrary order into fixed-capacity bins (own share included), which are exchanged

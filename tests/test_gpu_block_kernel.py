@@ -27,7 +27,7 @@ from tests.test_gpu_parity import Sim, assert_same_state
 pytestmark = pytest.mark.gpu
 
 BLOCK = "k_ps_block<GRID3D>"
-EPOCH, BATCH = 64, 1024  # gp_internal.hpp BLOCK_EPOCH, gp_api.hip BATCH
+EPOCH, BATCH = 64, 1024  # gp_internal.hpp BLOCK_EPOCH, gp_host.hpp BATCH
 
 
 def frozen(st):

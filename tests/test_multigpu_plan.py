@@ -1,6 +1,6 @@
 """CPU: the one-node 8-GPU plan of BASELINE's multi-GPU configurations, computed on
-the host (no GPU, no RCCL).  The library's slab plan (gp_api.hip make_bounds)
-and exchange capacities (gp_api.hip setup_exchange: expected messages per rank
+the host (no GPU, no RCCL).  The library's slab plan (gp_setup.hip make_bounds)
+and exchange capacities (gp_setup.hip setup_exchange: expected messages per rank
 pair + 12 sigma + 64) are restated here; the tests check that
 
   * C5 (Imp3D push-sum, n = 1e9) and C4 (full push-sum, n = 1e8) fit one

@@ -176,7 +176,7 @@ def model(tdir, n, topo, alg, W, rounds, out=None):
         for k in range(W):
             rank_ms[k].append(tr[k])
     # push-sum runs its exchange in two halves overlapped with the send / coarse passes
-    # (full, gp_api.hip launch_round_full_multi) or the pack / unpack (Imp3D, exchange):
+    # (full, gp_exchange.hip launch_round_full_multi) or the pack / unpack (Imp3D, exchange):
     # those kernels appear twice per slab
     halves = 2 if alg == "push-sum" and topo in ("full", "Imp3D") else 1
     if alg == "push-sum" and topo == "Imp3D":  # round 5: XREGIONS list regions (k_list_pack per region and slab)
@@ -197,7 +197,7 @@ def model(tdir, n, topo, alg, W, rounds, out=None):
     comp = [statistics.mean(v) for v in rank_ms]
     t_comp = max(comp)
     piped = None
-    # region-by-region rounds (gp_api.hip launch_round_regions): per rank the round kernel of
+    # region-by-region rounds (gp_exchange.hip launch_round_regions): per rank the round kernel of
     # region h, then region h's pack; region h's transfer after both, overlapping region h + 1
     rk_name = next((nm for nm in per_slab_names(groups, short) if nm.startswith("k_ps_tile")), None)
     nreg = 0
@@ -219,7 +219,7 @@ def model(tdir, n, topo, alg, W, rounds, out=None):
             regions = {"kernel_region_ms": [round(max(K[k][h] for k in range(W)), 4) for h in range(nreg)],
                        "pack_region_ms": [round(max(Pk[k][h] for k in range(W)), 4) for h in range(nreg)],
                        "K": K, "P": Pk}
-    # full push-sum (round 6, gp_api.hip launch_round_full_multi): per rank the splits of every
+    # full push-sum (round 6, gp_exchange.hip launch_round_full_multi): per rank the splits of every
     # region, then region by region the fold, whose messages travel (region h's transfer after
     # its fold, in order on the link) while the next region folds
     fused = None
