@@ -291,7 +291,8 @@ struct RoundArgs {
     uint32_t walk;  // 0: XCD-contiguous eighths, 1: one global sweep (tile t -> block t % grid), 2: x-windows,
                     // 3: x-windows claimed from per-XCD counters (k_ps_tile)
     uint32_t wx;    // walk 2: planes per x-window
-    uint32_t stage_cap;  // k_ps_tile: tiles with more in-edges take the unstaged path (tests force it)
+    uint32_t stage_cap;  // k_ps_tile, and k_gossip_tile in the experiments build: tiles with more in-edges
+                         // take the unstaged path (tests force it)
 #ifdef GP_EXPERIMENTS
     uint32_t no_full;    // k_ps_tile: every tile through the general (!FULL) tile body (GP_NO_FULLTILE=1)
 #endif

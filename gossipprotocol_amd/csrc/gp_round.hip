@@ -1117,7 +1117,12 @@ __global__ __launch_bounds__(TPB, GP_MINB) void k_gossip_tile(RoundArgs a, uint3
             b_xp = dma_stage_bytes(L.xp, a.nbc, (int64_t)j0 + G.g2, (int64_t)j1 + G.g2, a.ext_lo, a.ext_hi);
         }
         const uint32_t cnt = e_hi - e_lo;
+#ifdef GP_EXPERIMENTS
+        // GP_STAGE_CAP lowers the limit, so tiles take the unstaged path (parity tests); never raises it
+        const bool staged = cnt <= min((uint32_t)SRC_CAP, a.stage_cap);
+#else
         const bool staged = cnt <= (uint32_t)SRC_CAP;
+#endif
         int o_off = 0;  // L.off[jl + o_off] = in_off[T + jl]
         if (TOPO == IMP3D) {
             o_off = (int)dma_stage_words(L.off, a.in_off, j0, j1 + 1) - (int)(j0 - T);

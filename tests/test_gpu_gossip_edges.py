@@ -1,0 +1,261 @@
+"""GPU: the gossip round kernels at the edges of their data layout, against the CPU oracle,
+bit-exact (per-round alerts, and `c` and `flags` of every node at every checkpoint).
+
+Column march (k_gossip_col, gp_col.hip; forced with GP_KERNEL=col on the experiments build).  A
+wave owns 4 y-rows x 64 z-lanes and marches them along x through its x-segment.  The sizes put
+lattice edges on every boundary of that patch:
+  g = 2..5      fewer work items than the 8 XCD shares of item_range; one y-block, exact at g = 4
+                (`hpv` false through y0 + NR < g alone), a one-row partial second block at g = 5;
+  g = 7, 8      two y-blocks (the hym / hyp halo rows), g % 4 = 3 and 0;
+  g = 63..67    one z-segment a lane short; exactly full (lane 63 is the last column and must not
+                load z + 1); a second segment with 1, 2, 3 valid lanes, where lane 63 of segment 0
+                and lane 0 of segment 1 take z +- 1 from led[] instead of DPP; g % 4 = 3, 0, 1, 2, 3;
+  g = 128, 129  two full segments; a third with a single lane.
+GP_XSEGS forces the x-segmentation: one segment, uneven segments (8 planes as 3, 3, 2; 65 as 17,
+17, 17, 14), segments one plane long (`pf` never true) and more segments asked for than planes.
+The product never picks a segment shorter than 16 planes (choose_kernel): those cases pin
+make_wave_args and the pf / xb arithmetic, not a product configuration.  Virtual ranks give slabs
+with x_lo > 0 and base != lo, down to one plane per slab (both x halos remote); Imp3D across
+ranks is the REMOTE instantiation (rtg, the send bitmap, k_apply_bits).  GP_RQ8=0 runs the
+32-bit delivery counters (bytes are the default).
+
+Runs of g >= 63 stop after a fixed number of rounds.  Their last checkpoint must have every
+node reached (c >= 1) and at least half of them converged (c > 10) in the ORACLE's state --
+every patch position has then received, alerted and dropped deliveries to converged nodes.  The
+condition is asserted, never relaxed: a case that misses it gets more rounds or another seed.
+(Seed 3 serves all but Imp3D g = 66, where it strands a node whose neighbours all converged
+first: only the injector reaches it, one pick per round among 287 496 -- hence SEED.)
+
+Tile kernel (k_gossip_tile, gp_round.hip; GP_KERNEL=tile): the tile-edge sizes that
+test_gpu_fulltile.py justifies for push-sum (all tiles full, one full + one partial, a single
+partial tile, a last wave that is partial), the line at P = 1024, 1025, 2048, and the unstaged
+in-edge path, which no tile reaches by itself (more than SRC_CAP = 1536 in-edges against a mean
+of 1024): on the experiments build GP_STAGE_CAP lowers the limit.  n = 4096, seed 2: the four
+tiles hold 999 / 1042 / 1006 / 1049 in-edges (recounted below from Oracle.neighbors), so cap 0
+stages no tile, 1000 one, 1024 two; on two ranks the unstaged loop also takes its
+`rtag[e] == r` branch for senders on the other rank.
+
+Full gossip (k_full_gossip_send / _recv, and the k_fullm_* kernels on three ranks) at P - 1 = 1
+(uniform(.., 1)) and at populations around its 256-thread blocks and 2^16.
+
+Injector, two chunks (inj_find / inj_remove, 65536 ids per chunk): g = 41 has T = 68921, so the
+second chunk holds 3385 ids.  NOT covered here, and nowhere else in the suite: a long two-chunk
+run.  Gossip at g = 41 stalls at 0.83 T alerts within 500 rounds (3D 56 987, Imp3D 57 662 of
+68 921, seed 3); from there only the injector's one pick per round moves it (57 138 / 57 809 at
+round 3000), and 0.9 T -- the share from which picks mostly remove converged ids from both
+chunks -- is reached only in round 59 001..60 000 (3D) / 58 001..59 000 (Imp3D) of the 97 286 /
+97 560 the whole run takes: 50 to 60 s of oracle time per topology before the first compared
+round that meets it, as long as the run that drains the second chunk to empty (56 s).  Both are
+too long for this suite and remain unpinned; the two-chunk list is compared over its first 400
+rounds only (test_gpu_parity.py, 125 000 nodes).
+"""
+import functools
+from collections import Counter, namedtuple
+
+import numpy as np
+import pytest
+
+from tests.oracle_ctypes import Oracle
+from tests.test_gpu_parity import Sim
+
+pytestmark = pytest.mark.gpu
+
+Ref = namedtuple("Ref", "chk chunks rounds alerts_total T")
+
+
+def _frozen(st):
+    out = {k: st[k] for k in ("c", "flags")}
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def reference(n, topo, seed, rounds, chk):
+    """The oracle's gossip run, once per case: chunks = [(alerts of the chunk, state after it)].
+    rounds = None: through convergence (the loop is bounded by the oracle's own round count)."""
+    orc = Oracle(n, topo, "gossip", seed)
+    chunks = []
+    while orc.alerts_total < orc.T and (rounds is None or orc.rounds < rounds):
+        assert orc.rounds < 5000, "the oracle did not converge"
+        a = orc.step(chk)
+        chunks.append((a, _frozen(orc.state())))
+        if len(a) < chk:
+            break
+    ref = Ref(chk, chunks, orc.rounds, orc.alerts_total, orc.T)
+    orc.close()
+    return ref
+
+
+def check(sim, ref, name_has):
+    assert name_has in sim.kernel_stats()[2], sim.kernel_stats()[2]
+    for i, (oa, ost) in enumerate(ref.chunks):
+        ga = sim.step(ref.chk)
+        assert ga == oa, f"alerts differ in rounds {i * ref.chk}..{(i + 1) * ref.chk}"
+        gs = sim.state()
+        np.testing.assert_array_equal(gs["c"], ost["c"])
+        np.testing.assert_array_equal(gs["flags"], ost["flags"])
+    assert sim.rounds == ref.rounds and sim.alerts_total == ref.alerts_total
+
+
+def env(monkeypatch, kernel, **extra):
+    monkeypatch.setenv("GP_KERNEL", kernel)
+    for k, v in extra.items():
+        monkeypatch.setenv(k, str(v))
+
+
+# ---------------------------------------------------------------- column march
+COL = "k_gossip_col"
+FIXED = {"3D": 160, "Imp3D": 80}   # rounds of the g >= 63 runs, checkpoints every 40
+SEED = {("Imp3D", 66): 4}          # every other column case: seed 3 (module docstring)
+
+
+def col_ref(topo, g):
+    """Through convergence for g <= 8; FIXED rounds above, with the coverage condition asserted
+    from the oracle's last state."""
+    seed = SEED.get((topo, g), 3)
+    if g <= 8:
+        ref = reference(g ** 3, topo, seed, None, 100)
+        assert ref.alerts_total >= ref.T == g ** 3
+        return ref
+    ref = reference(g ** 3, topo, seed, FIXED[topo], 40)
+    c = ref.chunks[-1][1]["c"]
+    assert ref.rounds == FIXED[topo] and c.min() >= 1 and 2 * np.count_nonzero(c > 10) >= c.size, \
+        f"{topo} g={g}: not every node reached / half converged after {ref.rounds} rounds"
+    return ref
+
+
+def col_run(monkeypatch, topo, g, ranks=1, **extra):
+    env(monkeypatch, "col", **extra)
+    ref = col_ref(topo, g)
+    sim = Sim(g ** 3, topo, "gossip", seed=SEED.get((topo, g), 3), virtual_ranks=ranks, experimental=True)
+    assert sim.info().num_gpus == ranks and sim.info().grid == g
+    check(sim, ref, COL)
+    sim.close()
+
+
+@pytest.mark.parametrize("topo", ["3D", "Imp3D"])
+@pytest.mark.parametrize("g", [2, 3, 4, 5, 7, 8])
+def test_col_small_lattices_to_convergence(g, topo, monkeypatch):
+    """nitems < 8 (g <= 5), one exact / one partial y-block, two y-blocks with g % 4 = 3 and 0."""
+    col_run(monkeypatch, topo, g)
+
+
+@pytest.mark.parametrize("g,topo", [(g, t) for t in ("3D", "Imp3D") for g in (63, 64, 65, 66, 67)] +
+                         [(128, "Imp3D"), (129, "Imp3D")])
+def test_col_z_segment_edges(g, topo, monkeypatch):
+    """z extents around one and two waves: the led[] loads across a segment boundary, the last
+    column in lane 63, last segments of one to three lanes; every g % 4."""
+    col_run(monkeypatch, topo, g)
+
+
+@pytest.mark.parametrize("topo", ["3D", "Imp3D"])
+@pytest.mark.parametrize("g,xsegs", [(8, 1), (8, 3), (8, 8), (8, 64), (65, 1), (65, 4), (65, 65)])
+def test_col_x_segments(g, xsegs, topo, monkeypatch):
+    """GP_XSEGS: one segment; uneven ones (3, 3, 2 / 17, 17, 17, 14); one plane each (`pf` never
+    true); more asked for than planes.  The product keeps segments >= 16 planes (choose_kernel):
+    this pins make_wave_args and the pf / xb arithmetic, not a product configuration."""
+    col_run(monkeypatch, topo, g, GP_XSEGS=xsegs)
+
+
+@pytest.mark.parametrize("topo", ["3D", "Imp3D"])
+@pytest.mark.parametrize("g,ranks,xsegs", [(65, 2, None), (65, 5, None), (66, 4, None), (8, 8, None), (65, 2, 4)])
+def test_col_virtual_ranks(g, ranks, xsegs, topo, monkeypatch):
+    """Slabs with x_lo > 0 and base != lo: 32 + 33 planes, 13 each, 16 / 17, and one plane per
+    slab (both x halos remote, segment length 1); one case with the x-segmentation forced too.
+    Imp3D is the REMOTE instantiation."""
+    col_run(monkeypatch, topo, g, ranks=ranks, **({} if xsegs is None else {"GP_XSEGS": xsegs}))
+
+
+@pytest.mark.parametrize("ranks", [1, 3])
+def test_col_word_counters(ranks, monkeypatch):
+    """GP_RQ8=0: the random-edge delivery counts as 32-bit words (rq_add's and the kernel's
+    other branch; bytes are the default)."""
+    col_run(monkeypatch, "Imp3D", 65, ranks=ranks, GP_RQ8=0)
+
+
+# ---------------------------------------------------------------- tile kernel
+TILE = "k_gossip_tile"
+
+
+def tile_run(monkeypatch, n, topo, ranks=1, **extra):
+    env(monkeypatch, "tile", **extra)
+    ref = reference(n, topo, 2, 48, 8)
+    sim = Sim(n, topo, "gossip", seed=2, virtual_ranks=ranks, experimental=True)
+    assert sim.info().num_gpus == ranks
+    check(sim, ref, TILE)
+    sim.close()
+    return ref
+
+
+@pytest.mark.parametrize("topo", ["Imp3D", "3D"])
+@pytest.mark.parametrize("n", [4096, 1331, 1000, 9261])
+def test_tile_edge_sizes(n, topo, monkeypatch):
+    """All tiles full, one full + one partial, a single partial tile, a partial last wave."""
+    tile_run(monkeypatch, n, topo)
+
+
+@pytest.mark.parametrize("n", [1023, 1024, 2047, 1500])
+def test_tile_line(n, monkeypatch):
+    """The line at P = n + 1 = 1024, 1025 (a second tile of one node), 2048, and 1501."""
+    tile_run(monkeypatch, n, "line")
+
+
+@pytest.mark.parametrize("n", [4096, 1331])
+def test_tile_two_virtual_ranks(n, monkeypatch):
+    """Slabs that end on tile boundaries (8 planes of 256) and off them (5 / 6 planes of 121)."""
+    tile_run(monkeypatch, n, "Imp3D", ranks=2)
+
+
+@functools.lru_cache(maxsize=None)
+def tile_in_edges(n, seed):
+    """In-edges (random-edge senders) per 1024-node tile, from the oracle's neighbour lists: a
+    node's random edge is the neighbour that is not one of its lattice ones, or the one listed
+    twice."""
+    orc = Oracle(n, "Imp3D", "gossip", seed)
+    g = round(n ** (1 / 3))
+    assert g ** 3 == n == orc.P
+    cnt = np.zeros((n + 1023) // 1024, np.int64)
+    for i in range(n):
+        x, y, z = i // (g * g), i // g % g, i % g
+        lat = {j for j, ok in ((i - g * g, x > 0), (i + g * g, x < g - 1), (i - g, y > 0), (i + g, y < g - 1),
+                               (i - 1, z > 0), (i + 1, z < g - 1)) if ok}
+        nb = orc.neighbors(i)
+        assert len(nb) == len(lat) + 1 and lat <= set(nb)
+        rnd = [t for t in nb if t not in lat] or [t for t, k in Counter(nb).items() if k > 1]
+        assert len(rnd) == 1
+        cnt[rnd[0] // 1024] += 1
+    orc.close()
+    return tuple(int(v) for v in cnt)
+
+
+@pytest.mark.parametrize("ranks", [1, 2])
+@pytest.mark.parametrize("cap,staged", [(0, 0), (1000, 1), (1024, 2)])
+def test_tile_unstaged_in_edges(cap, staged, ranks, monkeypatch):
+    """GP_STAGE_CAP below the tiles' in-edge counts: the per-edge loop over in_src with the
+    bitmap (local sender) or rtag (sender on the other rank) read per edge, alone and mixed with
+    staged tiles, through activation into every node reached."""
+    edges = tile_in_edges(4096, 2)
+    assert edges == (999, 1042, 1006, 1049) and sum(e <= cap for e in edges) == staged
+    ref = tile_run(monkeypatch, 4096, "Imp3D", ranks=ranks, GP_STAGE_CAP=cap)
+    assert ref.chunks[-1][1]["c"].min() >= 1
+
+
+# ---------------------------------------------------------------- full topology
+@functools.lru_cache(maxsize=None)
+def full_ref(n):
+    """Through convergence where the oracle gets there within 600 rounds, else 300 rounds."""
+    ref = reference(n, "full", n + 3, 600, 100)
+    return ref if ref.alerts_total >= ref.T else reference(n, "full", n + 3, 300, 100)
+
+
+@pytest.mark.parametrize("n,ranks", [(n, 1) for n in (1, 2, 255, 256, 257, 65535, 65536)] +
+                         [(n, 3) for n in (255, 256, 257, 65535, 65536)])
+def test_full_gossip_sizes(n, ranks):
+    """P = n + 1 = 2 (every draw is uniform(.., 1)), 3, and populations around one 256-thread
+    block and 2^16; the product's kernels on one rank and on three."""
+    ref = full_ref(n)
+    sim = Sim(n, "full", "gossip", seed=n + 3, virtual_ranks=ranks)
+    assert sim.info().num_gpus == ranks and sim.population == n + 1
+    check(sim, ref, "k_full_gossip_send+recv")
+    sim.close()

@@ -156,14 +156,16 @@ def test_virtual_ranks_max_world(topo, alg):
     orc.close()
 
 
+@pytest.mark.parametrize("rq8", ["0", "1"])
 @pytest.mark.parametrize("ranks", [1, 3])
-def test_col_gossip_byte_counters(ranks, monkeypatch):
+def test_col_gossip_byte_counters(ranks, rq8, monkeypatch):
     """Imp3D gossip on the column kernel with the random-edge delivery counts held
-    as bytes, four per word (GP_RQ8=1, experiments build): local senders' atomics,
-    the exchange's counts and the seed's round-0 send all add into byte lanes --
-    bit-exact vs the oracle on one and on three ranks."""
+    as bytes, four per word (GP_RQ8=1, the default), and as 32-bit words (GP_RQ8=0,
+    experiments build): local senders' atomics, the exchange's counts and the seed's
+    round-0 send all add into byte lanes / words -- bit-exact vs the oracle on one
+    and on three ranks."""
     monkeypatch.setenv("GP_KERNEL", "col")
-    monkeypatch.setenv("GP_RQ8", "1")
+    monkeypatch.setenv("GP_RQ8", rq8)
     n, seed = 125000, 12
     sim = Sim(n, "Imp3D", "gossip", seed=seed, virtual_ranks=ranks, experimental=True)
     orc = Oracle(n, "Imp3D", "gossip", seed)
