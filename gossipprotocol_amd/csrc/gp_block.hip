@@ -13,7 +13,7 @@
 //     barrier (grid_sync), and every box reads its neighbours' facing layers into
 //     LDS halo arrays with device-coherent loads -- the only global traffic of a
 //     round (~28 KB per box at C2);
-//   * each node then folds exactly as the tile kernel (gp_round.hip) does: own half,
+//   * each node then folds exactly as the tile kernel (gp_ps_tile.hip) does: own half,
 //     lattice messages in the receiver's slot order (Program.fs:246-257), the ratio
 //     test of Program.fs:114-123 (SRS v1 B.4), the next direction by Philox -- with
 //     acc + m * 0.5, the oracle's own rounding;

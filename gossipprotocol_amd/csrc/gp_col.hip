@@ -1,7 +1,7 @@
 // gp_col.hip -- column-march round kernels for the 3D / Imp3D lattice (gfx950).
 //
 // Gossip: one synchronous round of SRS v1 in PULL form with 2.5-D
-// blocking (push-sum runs the tile kernel, gp_round.hip).  A wave owns a patch of 4 y-rows x 64 z-columns (one node per lane
+// blocking (push-sum runs the tile kernel, gp_ps_tile.hip).  A wave owns a patch of 4 y-rows x 64 z-columns (one node per lane
 // and row; node id = x*g^2 + y*g + z, lanes = consecutive z, so every row of a
 // patch is one coalesced 64-node segment) and marches it along x through its
 // x-segment.  Planes x and x+1 of the patch stay in registers and plane x+2 is

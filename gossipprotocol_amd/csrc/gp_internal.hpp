@@ -248,7 +248,7 @@ struct DevState {
     BlockPlan bplan;          // KERNEL_BLOCK (gp_block.hip): boxes, face buffer, barrier scratch
     void* bface;
     void* bscratch;
-    uint32_t tile_wide;       // KERNEL_TILE: the 1024-thread size class (gp_round_wide.hip)
+    uint32_t tile_wide;       // KERNEL_TILE: the 1024-thread size class (gp_ps_tile_wide.hip)
     // Imp3D: the rank's in-edge count
     uint32_t nedges;
     // walk 3 (dynamic tile queue): per round parity, 8 per-XCD item counters,
@@ -265,7 +265,10 @@ struct DevState {
 constexpr int TQ_STRIDE = 64;
 hipError_t launch_round_tile_region(const DevState& S, uint32_t round, uint32_t h, int grid, hipStream_t st);
 
-// Arguments of the tiled round kernels (gp_round.hip): only what they read.
+// Nodes per tile of the tiled round kernels, in both size classes (gp_tile.hpp).
+constexpr int TILE = 1024;
+
+// Arguments of the tiled round kernels (gp_ps_tile.hip, gp_gossip_tile.hip): only what they read.
 struct RoundArgs {
     const double2* swc;
     double2* swn;
@@ -353,10 +356,10 @@ int col_blocks_per_cu(int topo, int alg);
 // Imp3D gossip: count the seed's round-0 random-edge send at its target (rq)
 hipError_t launch_col_seed_init(const DevState& S, hipStream_t st);
 
-// ---- tiled round kernels (gp_round.hip)
+// ---- tiled round kernels: host side and set-up kernels (gp_tile_host.hip)
 uint32_t rbits_words_for(uint32_t lo, uint32_t nloc);
+RoundArgs make_round_args(const DevState& S, uint32_t round);
 hipError_t launch_round_tile(const DevState& S, uint32_t round, int grid, hipStream_t st);
-int ps_tile_resident_blocks(int topo, bool remote, int device);
 bool build_walk_list(const DevState& S, int NR, std::vector<uint32_t>& list, uint32_t woff[][9]);
 bool region_tiles(uint32_t lo, uint32_t nloc, uint64_t g2, int NR, uint32_t* rb);
 hipError_t launch_rbits_init(const DevState& S, int grid, hipStream_t st);
@@ -365,9 +368,14 @@ hipError_t launch_pack_ind4(const DevState& S, uint32_t wide_at, int grid, hipSt
 hipError_t launch_pack_src_deg(const uint32_t* src, uint32_t* out, uint32_t n, const Geom& G, int grid,
                                hipStream_t st);
 
-// ---- the same tiled kernels as the small-population size class (gp_round_wide.hip)
+// ---- the tile kernels behind launch_round_tile: push-sum (gp_ps_tile.hip), gossip (gp_gossip_tile.hip)
+hipError_t launch_ps_tile(const DevState& S, const RoundArgs& a, uint32_t round, int grid, hipStream_t st);
+int ps_tile_resident_blocks(int topo, bool remote, int device);
+hipError_t launch_gossip_tile(const DevState& S, const RoundArgs& a, uint32_t round, int grid, hipStream_t st);
+
+// ---- the push-sum tile kernel as the small-population size class, line and 3D only (gp_ps_tile_wide.hip)
 namespace wide {
-hipError_t launch_round_tile(const DevState& S, uint32_t round, int grid, hipStream_t st);
+hipError_t launch_ps_tile(const DevState& S, const RoundArgs& a, uint32_t round, int grid, hipStream_t st);
 int ps_tile_resident_blocks(int topo, bool remote, int device);
 }  // namespace wide
 

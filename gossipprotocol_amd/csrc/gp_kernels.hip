@@ -2,7 +2,7 @@
 // push-sum round (SRS v1).
 //
 // Design:
-//   * the per-round bulk kernels for line / 3D / Imp3D live in gp_round.hip;
+//   * the per-round bulk kernels for line / 3D / Imp3D live in gp_ps_tile.hip and gp_gossip_tile.hip;
 //     this file holds setup kernels, the full-topology round and the finalize
 //     kernel;
 //   * state is double-buffered (round r reads buffer r&1, writes r&1^1), so the
@@ -379,8 +379,7 @@ hipError_t launch_histogram(const uint32_t* keys, uint32_t n, uint32_t* counts, 
 hipError_t launch_bulk(const DevState& S, uint32_t round, int grid, hipStream_t st) {
     const dim3 g(grid), b(BULK_THREADS);
     if (S.topo != FULL) {
-        if (S.kernel == KERNEL_TILE)
-            return S.tile_wide ? wide::launch_round_tile(S, round, grid, st) : launch_round_tile(S, round, grid, st);
+        if (S.kernel == KERNEL_TILE) return launch_round_tile(S, round, grid, st);
         if (S.kernel == KERNEL_COL) return launch_round_col(make_wave_args(S, round), S.topo, S.alg, round, grid, st);
         return hipErrorInvalidValue;
     }
@@ -403,12 +402,9 @@ const char* bulk_kernel_name(const DevState& S) {
     if (S.topo == FULL && S.alg == PUSHSUM && S.fb_fused) return "k_fb_split+fold<send>";  // one rank, fused
     if (S.kernel == KERNEL_BLOCK) return "k_ps_block<GRID3D>";  // LDS-resident, one launch per batch
     const int v = S.kernel == KERNEL_COL ? 1 : 0;
-    if (v == 0 && S.tile_wide && S.topo != FULL) {  // the 1024-thread size class (gp_round_wide.hip)
-        static const char* w[2][4] = {{"wide::k_gossip_tile<LINE>", "", "wide::k_gossip_tile<GRID3D>",
-                                       "wide::k_gossip_tile<IMP3D>"},
-                                      {"wide::k_ps_tile<LINE>", "", "wide::k_ps_tile<GRID3D>", "wide::k_ps_tile<IMP3D>"}};
-        return w[S.alg == PUSHSUM ? 1 : 0][S.topo];
-    }
+    // the 1024-thread size class (gp_ps_tile_wide.hip): line and 3D push-sum
+    if (v == 0 && S.tile_wide && S.alg == PUSHSUM && (S.topo == LINE || S.topo == GRID3D))
+        return S.topo == LINE ? "wide::k_ps_tile<LINE>" : "wide::k_ps_tile<GRID3D>";
     return S.alg == PUSHSUM ? ps[v][S.topo] : go[v][S.topo];
 }
 

@@ -1,13 +1,14 @@
-// gp_round.hip -- the per-round bulk kernels for line / 3D / Imp3D (gfx950).
+// gp_ps_tile.hip -- the push-sum tile kernel for line / 3D / Imp3D (gfx950).
 //
 // One synchronous round of SRS v1 in PULL form: every node
 // reads who sent to it and folds the messages in canonical order, then draws
 // its own direction for the next round.  Layout per workgroup (256 threads,
-// TILE = 1024 consecutive nodes, 4 per thread, lane-contiguous):
+// TILE = 1024 consecutive nodes, 4 per thread, lane-contiguous; gp_tile.hpp):
 //
-//   1. stage in LDS with wide coalesced loads: the direction bytes of the tile
-//      and its +-g rows (y/z neighbours, or +-1 for line), the x-1 and x+1
-//      plane segments (3D), the tile's in-list offsets and senders (Imp3D);
+//   1. stage in LDS by LDS-DMA: the direction bytes of the tile and its +-g rows
+//      (y/z neighbours, or +-1 for line), the x-1 and x+1 plane segments (3D),
+//      the tile's nibble in-degrees (Imp3D: DevState::ind4; in_off itself is read
+//      only for the tile's range and inside `wide` tiles);
 //   2. per node: lattice senders are read from LDS and only the (s, w) of the
 //      neighbours that actually sent here are gathered (independent loads, no
 //      dependent byte loads); Imp3D in-edges decide "sent on its random edge"
@@ -17,29 +18,16 @@
 //      ascending sender), ratio test, next-round Philox draw; node bytes leave
 //      through LDS as 32-bit words, random-edge bits as one 64-bit ballot per
 //      wave.
-// Tiles are walked XCD-contiguously (blocks b and b+8 share an XCD on
-// MI355X), so the +-g rows a tile gathers from were just read by its XCD.
 // Built with -ffp-contract=off: the fold must round exactly like the oracle.
-#include <algorithm>
 #include <type_traits>
-#include <vector>
 
-#include "gp_internal.hpp"
+#include "gp_tile.hpp"
 
 namespace gp {
-#ifdef GP_ROUND_WIDE
-// gp_round_wide.hip: this file again with 1024-thread tiles of one node per
-// thread (the small-population size class), its host entry points in gp::wide
+#ifdef GP_TILE_WIDE
+// gp_ps_tile_wide.hip: this file again with 1024-thread tiles of one node per thread (the
+// small-population size class), line and 3D only, its host entry points in gp::wide
 namespace wide {
-#endif
-
-// Size class: gp_round_wide.hip defines these before including this file.
-#ifndef GP_ROUND_WIDE
-#define GP_TPB 256
-#define GP_NPT 4
-// __launch_bounds__ minimum waves per SIMD (= resident 256-thread blocks per CU): the LDS
-// tile allows 5, so keep VGPRs <= 96 to not lose the fifth
-#define GP_MINB 5
 #endif
 
 // Measured choices of the push-sum tile kernel (the rejected alternatives and their
@@ -57,28 +45,6 @@ namespace wide {
 constexpr int PRIO = 1;  // the raised wave priority
 
 namespace {
-
-constexpr int TPB = GP_TPB;                // 256 (wide size class: 1024)
-constexpr int NPT = GP_NPT;                // nodes per thread per tile
-constexpr int TILE = TPB * NPT;            // 1024
-constexpr int HMAX = 1625;                 // largest lattice edge with g^3 < 2^32
-constexpr int W_ROWS = (TILE + 2 * HMAX) / 4 + 4;
-constexpr int W_PLANE = TILE / 4 + 4;
-constexpr int SRC_CAP = TILE * 3 / 2;       // gossip: staged in-list entries per tile (mean TILE)
-
-// Staged ranges are moved by 16-byte LDS-DMA (global_load_lds_dwordx4) from a
-// 16-byte aligned start: every array has 8 words of slack for the alignment.
-constexpr int DMA_SLACK = 8;
-
-struct TileLds {
-    uint32_t rows[W_ROWS + DMA_SLACK];   // direction bytes of [j0 - H, j1 + H)
-    uint32_t xm[W_PLANE + DMA_SLACK];    // direction bytes of [j0 - g^2, j1 - g^2)
-    uint32_t xp[W_PLANE + DMA_SLACK];    // direction bytes of [j0 + g^2, j1 + g^2)
-    uint32_t off[TILE + 1 + DMA_SLACK];  // in_off[j0 .. j1]
-    uint32_t sent[SRC_CAP / 4];          // byte per staged in-edge: its sender used the random edge
-    uint32_t out[TILE / 4];              // next-round node bytes, stored as words
-    uint32_t red[2][TPB / 64];
-};
 
 // k_ps_tile: the tile decides its in-edges itself.  The used in-edges' (s, w) are gathered by LDS-DMA straight into per-edge
 // slots (edge q's message at slot q -- lane-linear, so one global_load_lds per
@@ -115,199 +81,6 @@ struct TileLdsP {
     double2 zb[TPB / 64][NPT][2];     // (s, w) across each wave's ends, slot k: [0] node - 1, [1] node + 64
 };
 
-// set bits of m below this lane
-__device__ __forceinline__ uint32_t mbcnt64(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-__device__ __forceinline__ uint32_t lds_byte(const uint32_t* w, uint32_t idx) {
-    return reinterpret_cast<const uint8_t*>(w)[idx];
-}
-
-typedef __attribute__((address_space(1))) void gvoid_t;
-typedef __attribute__((address_space(3))) void lvoid_t;
-
-// Copy nbytes (rounded up to 16) from a 16-byte aligned global address into LDS
-// with LDS-DMA: no VGPR round trip and no wait inside the loop, so every
-// staging copy of a tile is in flight at once (retired by the next
-// __syncthreads, which waits vmcnt(0)).  One wave-instruction moves 1 KiB.
-template <int AUX = 0>
-__device__ __forceinline__ void dma_copy(void* lds, const char* g16, uint32_t nbytes) {
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t c = (threadIdx.x >> 6) * 1024u; c < nbytes; c += TPB * 16u) {
-        const uint32_t o = c + lane * 16u;
-        if (o < nbytes)
-            __builtin_amdgcn_global_load_lds((gvoid_t*)(g16 + o), (lvoid_t*)(reinterpret_cast<char*>(lds) + c), 16, 0,
-                                             AUX);
-    }
-}
-// cache-policy bits of a single-use (streamed once per round) staging copy: nt
-constexpr int DMA_ONCE = 2;
-
-// Node bytes nb[lo, hi) clamped to [ext_lo,
-// ext_hi); returns the node id of LDS byte 0 (up to 15 bytes below lo).  Reads
-// at most 15 bytes past hi (node arrays are padded).
-__device__ __forceinline__ uint32_t dma_stage_bytes(uint32_t* lds, const uint8_t* nb, int64_t lo, int64_t hi,
-                                                    uint32_t ext_lo, uint32_t ext_hi) {
-    if (lo < (int64_t)ext_lo) lo = ext_lo;
-    if (hi > (int64_t)ext_hi) hi = ext_hi;
-    const char* p = reinterpret_cast<const char*>(nb + lo);
-    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u);
-    if (hi > lo) dma_copy(lds, p - mis, (uint32_t)(hi - lo) + mis);
-    return (uint32_t)lo - mis;
-}
-
-// LDS-DMA of the words w[lo, hi); returns how many words below lo were staged
-// (w[lo + i] lands in lds[i + returned]).  Reads at most 3 words past hi
-// (the in-list arrays are padded).
-__device__ __forceinline__ uint32_t dma_stage_words(uint32_t* lds, const uint32_t* w, uint32_t lo, uint32_t hi) {
-    const char* p = reinterpret_cast<const char*>(w + lo);
-    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u);
-    if (hi > lo) dma_copy<DMA_ONCE>(lds, p - mis, (hi - lo) * 4u + mis);
-    return mis >> 2;
-}
-
-template <typename T>
-__device__ __forceinline__ T ld_agent(const T* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Tile walks (speed only -- any placement is correct; every tile of the slab
-// is visited exactly once).  Blocks with equal blockIdx % 8 share an XCD.
-//   walk 0: XCD-contiguous eighths of the tile range;
-//   walk 1: one global sweep (tile t -> block t % grid);
-//   walk 2 (3D / Imp3D): x-window walk.  Each XCD owns an eighth of the slab's
-//     x-planes, cut into windows of ~wx planes; inside a window the walk is
-//     x-fastest: item u -> plane x = x_w + u % nx_w, k-th tile starting in that
-//     plane.  The blocks resident on an XCD at one time then work on the same
-//     in-plane position of ~wx consecutive planes (x+-1 neighbours) and of a few
-//     consecutive k (y+-1 rows), so lattice gathers and the x+-1 byte planes hit
-//     the XCD's L2 instead of HBM.
-//   walk 3 (k_ps_tile): walk 2's items without the empty ones, listed per XCD
-//     at create time (DevState::wtiles, build_walk_list for gp_setup.hip) and
-//     claimed in order from a per-XCD counter (one returning atomic per tile,
-//     issued a tile ahead) on a grid of exactly the resident blocks.  The tiles
-//     an XCD has in flight are then always ~160 consecutive items (20 in-plane
-//     positions of 8 planes), and the tiles just finished are their y-1 / x+-1
-//     neighbours; walk 2's static stride keeps items 2048 apart in flight, and
-//     its item -> tile arithmetic (64-bit divisions) costs ~100 scalar
-//     instructions per tile and wave.
-struct TileWalk {
-    uint32_t t, end, step;
-    // walk 2
-    uint32_t mode, tb, tend, g2, x0, xa, nxa, kp, nwin;
-    // walk 3: this XCD's item counter and tile list
-    uint32_t* qc;
-    const uint32_t* wl;
-    __device__ TileWalk(const RoundArgs& a) {
-        const uint32_t G = gridDim.x;
-        mode = a.walk;
-        qc = nullptr;
-        wl = nullptr;
-        if (mode == 3 && (a.wt == nullptr || G < 8 || (G & 7) != 0)) mode = 1;
-        if (mode == 3) {
-            const uint32_t c = blockIdx.x & 7;
-            qc = a.tq + c * TQ_STRIDE;
-            wl = a.wt + a.wo[c];
-            t = 0;
-            end = a.wo[c + 1] - a.wo[c];
-            step = 1;
-        } else if (mode == 2 && a.G.g2 && G >= 8 && (G & 7) == 0) {
-            const uint32_t c = blockIdx.x & 7;
-            g2 = a.G.g2;
-            tb = a.lo / TILE;
-            tend = (uint32_t)(((uint64_t)a.lo + a.nloc + TILE - 1) / TILE);
-            x0 = a.lo / g2;
-            const uint32_t X0 = x0, nx = a.nloc / g2;
-            xa = X0 + (uint32_t)((uint64_t)nx * c / 8);
-            nxa = X0 + (uint32_t)((uint64_t)nx * (c + 1) / 8) - xa;
-            kp = (g2 + TILE - 1) / TILE + 1;
-            nwin = a.wx ? (nxa + a.wx - 1) / a.wx : 1u;
-            if (nwin == 0) nwin = 1;
-            t = blockIdx.x >> 3;
-            end = nxa * kp;
-            step = G >> 3;
-        } else if (mode == 0 && G >= 8 && (G & 7) == 0) {
-            mode = 0;
-            const uint32_t x = blockIdx.x & 7, k = blockIdx.x >> 3;
-            const uint32_t lo = (uint32_t)((uint64_t)a.ntiles * x / 8);
-            end = (uint32_t)((uint64_t)a.ntiles * (x + 1) / 8);
-            t = lo + k;
-            step = G >> 3;
-        } else {
-            mode = 1;
-            t = blockIdx.x;
-            end = a.ntiles;
-            step = G;
-        }
-    }
-    // first global tile index of plane x (the slab's first tile may start below lo)
-    __device__ __forceinline__ uint32_t first(uint32_t x) const {
-        return x <= x0 ? tb : min((uint32_t)(((uint64_t)x * g2 + TILE - 1) / TILE), tend);
-    }
-    // tile (relative to lo / TILE) of walk item t; false: empty item (block-uniform)
-    __device__ __forceinline__ bool tile(uint32_t& rel) const {
-        if (mode == 3) {
-            rel = ld_const(wl + t);
-            return true;
-        }
-        if (mode != 2) {
-            rel = t;
-            return true;
-        }
-        // (the divisors opaque: their reciprocals are then computed here, per item, instead of being
-        // hoisted out of the caller's tile loop into VGPRs that stay live across its node phase)
-        uint32_t kp = this->kp, nwin = this->nwin, nxa = this->nxa;
-        asm volatile("" : "+s"(kp), "+s"(nwin), "+s"(nxa));
-        const uint32_t pl = t / kp;  // planes of this XCD before the item's window start (approx.)
-        uint32_t v = (uint32_t)((uint64_t)pl * nwin / nxa);
-        if (v >= nwin) v = nwin - 1;
-        uint32_t xs = (uint32_t)((uint64_t)nxa * v / nwin);
-        while (v > 0 && xs * kp > t) {
-            --v;
-            xs = (uint32_t)((uint64_t)nxa * v / nwin);
-        }
-        for (;;) {
-            const uint32_t xe = (uint32_t)((uint64_t)nxa * (v + 1) / nwin);
-            if (v + 1 >= nwin || xe * kp > t) break;
-            ++v;
-            xs = xe;
-        }
-        const uint32_t xe = (uint32_t)((uint64_t)nxa * (v + 1) / nwin);
-        const uint32_t u = t - xs * kp, nxv = xe - xs;
-        const uint32_t x = xa + xs + u % nxv, k = u / nxv;
-        const uint32_t ti = first(x) + k;
-        if (ti >= first(x + 1)) return false;
-        rel = ti - tb;
-        return true;
-    }
-};
-
-__device__ __forceinline__ double2 ld_sw(const double2* p) { return *p; }
-
-// v of another lane of the wave by DPP (CTRL 0x130 wave_shl:1 = lane + 1's,
-// 0x138 wave_shr:1 = lane - 1's; the lane at the wave's end gets 0 -- bound_ctrl,
-// so no zeroed destination register is needed)
-template <int CTRL>
-__device__ __forceinline__ double2 dpp_double2(double2 v) {
-    auto mv = [](double d) {
-        const uint64_t u = __builtin_bit_cast(uint64_t, d);
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xF, 0xF, true);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, true);
-        return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-    };
-    return make_double2(mv(v.x), mv(v.y));
-}
-
-// Next-round state is written once and not read again this round: non-temporal
-// stores keep it from displacing the current round's (s, w) in the XCD's L2,
-// where the neighbouring tiles' lattice gathers look for it.
-__device__ __forceinline__ void st_stream(double2* p, double2 v) {
-    __builtin_nontemporal_store(v.x, &p->x);
-    __builtin_nontemporal_store(v.y, &p->y);
-}
-__device__ __forceinline__ void st_stream(uint32_t* p, uint32_t v) { __builtin_nontemporal_store(v, p); }
-
 }  // namespace
 
 // ---------------------------------------------------------------- push-sum
@@ -323,7 +96,8 @@ __device__ __forceinline__ void st_stream(uint32_t* p, uint32_t v) { __builtin_n
 //      activation: the ballot-packed bitmap.  Used edges' (s, w) are gathered by
 //      LDS-DMA into slot q (edge order);
 //   2. staging by LDS-DMA: node bytes of the tile, its +-g rows and +-g^2 plane
-//      segments, the tile's in-list offsets; own (s, w) to registers;
+//      segments, (s, w) across each wave's ends, the tile's nibble in-degrees
+//      (Imp3D), whose prefix sums give each node's in-edge range;
 //   3. per node: lattice senders from the staged bytes, one gather per
 //      direction (no sender: the zero sentinel), the canonical fold (own half,
 //      lattice slots in slot order, random edges by ascending sender), the ratio
@@ -402,6 +176,10 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
         }
         const uint32_t cnt = e_hi - e_lo;
         const bool staged = cnt <= cap;
+        // static walks: the next tile's in-edge range (two uniform loads, consumed next tile).
+        // (Walk 3 does the same below, once its next item is known; written out twice: as one
+        // helper given the walk position, the Imp3D kernels' instructions changed,
+        // profiles/tile_split/isa_diff.txt.)
         if (TOPO == IMP3D && !dyn) {
             TileWalk nw = tw;
             nw.t += nw.step;
@@ -991,7 +769,7 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
         if (full) tile_body(std::true_type{});
         else tile_body(std::false_type{});
         // no barrier here: the next tile's in-edge pass and staging copies write
-        // bits / msg / rows / xm / xp / off, none of which this byte output reads,
+        // bits / msg / rows / xm / xp / ind, none of which this byte output reads,
         // and its node phase writes L.out only after its staging barrier
         tw.t = t_next;
     }
@@ -1077,310 +855,42 @@ __global__ __launch_bounds__(TPB, GP_MINB) void k_ps_tile(RoundArgs a, uint32_t 
     }
 }
 
-// ---------------------------------------------------------------- gossip
-// Deliveries to j = lattice senders pointing here + Imp3D random-edge senders
-// (bitmap) + the injector; all dropped if j was converged at round start.
-template <int TOPO, bool REMOTE>
-__global__ __launch_bounds__(TPB, GP_MINB) void k_gossip_tile(RoundArgs a, uint32_t r) {
-    __shared__ TileLds L;
-    Ctl* ctl = a.ctl;
-    if (ld_agent(&ctl->done)) return;
-    const long long inj = ld_agent(&ctl->inj_target);
-    const Geom G = a.G;
-    const uint32_t H = TOPO == LINE ? 1u : G.g;
-    uint32_t alerts = 0;
-    const int lane = threadIdx.x & 63;
 
-    for (TileWalk tw(a); tw.t < tw.end; tw.t += tw.step) {
-        uint32_t ti;
-        if (!tw.tile(ti)) continue;
-        // tiles sit on global multiples of TILE (4-aligned word I/O, 64-aligned
-        // ballot words); the slab's first and last tile may be partial
-        const uint32_t T = (a.lo / TILE + ti) * TILE;
-        const uint32_t j0 = max(a.lo, T);
-        const uint32_t j1 = min(a.lo + a.nloc, T + TILE);
-        uint32_t e_lo = 0, e_hi = 0;
-        if (TOPO == IMP3D) {
-            e_lo = ld_const(a.in_off + j0);
-            e_hi = ld_const(a.in_off + j1);
-        }
-        int32_t c0[NPT];
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-            const uint32_t j = T + k * TPB + threadIdx.x;
-            c0[k] = (j >= j0 && j < j1) ? a.c[j] : (int32_t)GOSSIP_DONE;
-        }
-        const uint32_t b_rows = dma_stage_bytes(L.rows, a.nbc, (int64_t)j0 - H, (int64_t)j1 + H, a.ext_lo, a.ext_hi);
-        uint32_t b_xm = 0, b_xp = 0;
-        if (TOPO != LINE) {
-            b_xm = dma_stage_bytes(L.xm, a.nbc, (int64_t)j0 - G.g2, (int64_t)j1 - G.g2, a.ext_lo, a.ext_hi);
-            b_xp = dma_stage_bytes(L.xp, a.nbc, (int64_t)j0 + G.g2, (int64_t)j1 + G.g2, a.ext_lo, a.ext_hi);
-        }
-        const uint32_t cnt = e_hi - e_lo;
-#ifdef GP_EXPERIMENTS
-        // GP_STAGE_CAP lowers the limit, so tiles take the unstaged path (parity tests); never raises it
-        const bool staged = cnt <= min((uint32_t)SRC_CAP, a.stage_cap);
-#else
-        const bool staged = cnt <= (uint32_t)SRC_CAP;
+// The kernel of a topology (remote: the Imp3D slab of a multi-rank run, whose in-edge
+// senders may live on other ranks); null where this size class does not build one.
+using PsTileKernel = void (*)(RoundArgs, uint32_t);
+static PsTileKernel ps_tile_kernel(int topo, bool remote) {
+    if (topo == LINE) return k_ps_tile<LINE, false>;
+    if (topo == GRID3D) return k_ps_tile<GRID3D, false>;
+#ifndef GP_TILE_WIDE
+    if (topo == IMP3D) return remote ? k_ps_tile<IMP3D, true> : k_ps_tile<IMP3D, false>;
 #endif
-        int o_off = 0;  // L.off[jl + o_off] = in_off[T + jl]
-        if (TOPO == IMP3D) {
-            o_off = (int)dma_stage_words(L.off, a.in_off, j0, j1 + 1) - (int)(j0 - T);
-            if (staged) {
-                // all sender loads, then all bitmap loads, in flight together
-                constexpr int FU = SRC_CAP / TPB;
-                uint32_t isrc[FU];
-#pragma unroll
-                for (int m = 0; m < FU; ++m) {
-                    const uint32_t q = threadIdx.x + m * TPB;
-                    isrc[m] = q < cnt ? a.in_src[e_lo + q] : 0u;
-                }
-                // the senders' direction draws of round r as one Philox batch; the
-                // bitmap (bit = active and the draw picks the random slot) is read
-                // only where the draw picks it, ~1/7 of the in-edges, instead of a
-                // random 128-byte line per in-edge
-                uint32_t X[FU], Y[FU];
-                philox2_batch<FU>(isrc, r, S_GOSSIP, a.k0, a.k1, X, Y);
-                unsigned long long wv[FU];
-#pragma unroll
-                for (int m = 0; m < FU; ++m) {
-                    const uint32_t q = threadIdx.x + m * TPB;
-                    const uint32_t li = isrc[m] - a.lo;
-                    const uint32_t di = popc6(present_mask<IMP3D>(isrc[m], G)) + 1u;
-                    const bool pick = uniform_from(X[m], Y[m], di) == di - 1u;
-                    wv[m] = q >= cnt ? 0ull
-                            : (!REMOTE || li < a.nloc) ? (pick ? a.rbc[(isrc[m] >> 6) - (a.lo >> 6)] : 0ull)
-                                          : (a.rtag[e_lo + q] == r ? ~0ull : 0ull);
-                }
-#pragma unroll
-                for (int m = 0; m < FU; ++m) {
-                    const uint32_t q = threadIdx.x + m * TPB;
-                    if (q < cnt)
-                        reinterpret_cast<uint8_t*>(L.sent)[q] = (uint8_t)((wv[m] >> (isrc[m] & 63)) & 1ull);
-                }
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-            const uint32_t jl = k * TPB + threadIdx.x;
-            const uint32_t j = T + jl;
-            const bool valid = j >= j0 && j < j1;
-            uint32_t dir = DIR_NONE;
-            if (valid) {
-                const uint32_t mask = present_mask<TOPO>(j, G);
-                int32_t c1 = c0[k];
-                if (c1 < (int32_t)GOSSIP_DONE) {
-                    uint32_t inc = (long long)j == inj ? 1u : 0u;
-                    if (TOPO == LINE) {
-                        inc += (mask & 1u) && (lds_byte(L.rows, j - 1 - b_rows) & DIR_MASK) == 1u;
-                        inc += (mask & 2u) && (lds_byte(L.rows, j + 1 - b_rows) & DIR_MASK) == 0u;
-                    } else {
-                        inc += (mask & 1u) && (lds_byte(L.xm, j - G.g2 - b_xm) & DIR_MASK) == 1u;
-                        inc += (mask & 2u) && (lds_byte(L.xp, j + G.g2 - b_xp) & DIR_MASK) == 0u;
-                        inc += (mask & 4u) && (lds_byte(L.rows, j + G.g - b_rows) & DIR_MASK) == 3u;
-                        inc += (mask & 8u) && (lds_byte(L.rows, j - G.g - b_rows) & DIR_MASK) == 2u;
-                        inc += (mask & 16u) && (lds_byte(L.rows, j + 1 - b_rows) & DIR_MASK) == 5u;
-                        inc += (mask & 32u) && (lds_byte(L.rows, j - 1 - b_rows) & DIR_MASK) == 4u;
-                    }
-                    if (TOPO == IMP3D) {
-                        const uint32_t e_b = L.off[jl + o_off], e_e = L.off[jl + 1 + o_off];
-                        if (staged) {
-                            for (uint32_t e = e_b; e < e_e; ++e) inc += lds_byte(L.sent, e - e_lo);
-                        } else {
-                            for (uint32_t e = e_b; e < e_e; ++e) {
-                                const uint32_t i = a.in_src[e];
-                                const uint32_t li = i - a.lo;
-                                inc += (!REMOTE || li < a.nloc) ? (uint32_t)((a.rbc[(i >> 6) - (a.lo >> 6)] >> (i & 63)) & 1ull)
-                                                   : (a.rtag[e] == r ? 1u : 0u);
-                            }
-                        }
-                    }
-                    if (inc) {
-                        c1 += (int32_t)inc;
-                        a.c[j] = c1;
-                        alerts += c1 > 10;  // the receipt that finds rumours == 10 (Program.fs:92-94)
-                    }
-                }
-                const bool active = ((j == a.seed_node) || c1 >= 1) && c1 <= 10;
-                if (active) {
-                    const uint32_t deg = popc6(mask) + (TOPO == IMP3D ? 1u : 0u);
-                    if (deg > 0) dir = slot_to_dir(mask, uniform(a.k0, a.k1, S_GOSSIP, j, r + 1, deg));
-                }
-                reinterpret_cast<uint8_t*>(L.out)[jl] = (uint8_t)dir;
-            }
-            if (TOPO == IMP3D) {
-                const unsigned long long bits = __ballot(valid && dir == DIR_RANDOM);
-                if (lane == 0) {  // the slab's first tile may start below lo: no word there
-                    const int64_t wi = (int64_t)((T + k * TPB + (threadIdx.x & ~63u)) >> 6) - (int64_t)(a.lo >> 6);
-                    if (wi >= 0) a.rbn[wi] = bits;
-                }
-            }
-        }
-        __syncthreads();
-        for (uint32_t w = threadIdx.x; w < (uint32_t)(TILE / 4); w += TPB) {
-            const uint32_t jw = T + w * 4;
-            if (jw >= j0 && jw + 4 <= j1) {
-                reinterpret_cast<uint32_t*>(a.nbn + T)[w] = L.out[w];
-            } else {
-                for (uint32_t b = 0; b < 4; ++b)
-                    if (jw + b >= j0 && jw + b < j1) a.nbn[jw + b] = reinterpret_cast<const uint8_t*>(L.out)[w * 4 + b];
-            }
-        }
-        __syncthreads();
-    }
-    uint32_t x = alerts;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    if (lane == 0) L.red[0][threadIdx.x >> 6] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        x = 0;
-        for (int w = 0; w < TPB / 64; ++w) x += L.red[0][w];
-        if (x) atomicAdd(&ctl->round_alerts, (unsigned long long)x);
-    }
+    return nullptr;
 }
 
-// Random-edge bits of round 0 (only the seed can be sending).
-// nb indexed by global id; bit (j - lo) of rb for the slab's nodes.
-// Word w holds ids [64 (w + lo/64), +64) (global 64-alignment, as the round kernels).
-__global__ __launch_bounds__(TPB) void k_rbits_init(const uint8_t* nb, uint64_t* rb, uint32_t lo, uint32_t nloc,
-                                                    uint32_t nwords) {
-    const uint32_t j00 = lo & ~63u;
-    for (uint32_t jb = blockIdx.x * TPB; jb < nwords * 64u; jb += gridDim.x * TPB) {
-        const uint32_t j = j00 + jb + threadIdx.x;
-        const bool bit = j >= lo && j - lo < nloc && (nb[j] & DIR_MASK) == DIR_RANDOM;
-        const unsigned long long bits = __ballot(bit);
-        if ((threadIdx.x & 63) == 0) rb[(j >> 6) - (lo >> 6)] = bits;
-    }
-}
-
-// Tiles covering the ids [lo, lo + nloc) (tiles sit on global multiples of TILE).
-static uint32_t tiles_for(uint32_t lo, uint32_t nloc) {
-    return (uint32_t)(((uint64_t)lo + nloc + TILE - 1) / TILE - lo / TILE);
-}
-// 64-bit words the ballot stores of one round touch (whole tiles) plus slack.
-uint32_t rbits_words_for(uint32_t lo, uint32_t nloc) { return tiles_for(lo, nloc) * (TILE / 64) + 16u; }
-
-RoundArgs make_round_args(const DevState& S, uint32_t round) {
-    const int cur = round & 1;
-    RoundArgs a;
-    // node arrays indexed by global id: pointers offset by the slab's first id
-    a.swc = S.sw[cur] ? S.sw[cur] - S.base : nullptr;
-    a.swn = S.sw[cur ^ 1] ? S.sw[cur ^ 1] - S.base : nullptr;
-    a.nbc = S.nb[cur] ? S.nb[cur] - S.base : nullptr;
-    a.nbn = S.nb[cur ^ 1] ? S.nb[cur ^ 1] - S.base : nullptr;
-    a.rbc = S.rbits[cur];
-    a.rbn = S.rbits[cur ^ 1];
-    a.in_off = S.in_off ? S.in_off - S.lo : nullptr;
-    a.in_src = S.in_src;
-    a.in_srcd = S.in_srcd;
-    a.ind4 = S.ind4 ? S.ind4 - (S.lo / TILE) * (TILE / 2) : nullptr;
-    a.rtag = S.rtag;
-    a.rmsg = S.rmsg;
-    a.rk = S.rk;
-    a.xhdr = S.xhdr[round & 1];
-    a.xvals = S.xvals[round & 1];
-    a.xnv = S.xnv;
-    a.c = S.c ? S.c - S.lo : nullptr;
-    a.lo = S.lo;
-    a.nloc = S.nloc;
-    a.ext_lo = S.ext_lo;
-    a.ext_hi = S.ext_hi;
-    a.ctl = S.ctl;
-    a.G = S.G;
-    a.k0 = S.k0;
-    a.k1 = S.k1;
-    a.seed_node = S.seed_node;
-    a.ntiles = tiles_for(S.lo, S.nloc);
-    a.walk = S.tile_walk;
-    a.stage_cap = S.tile_stage_cap;
-#ifdef GP_EXPERIMENTS
-    a.no_full = S.tile_no_full;
-#endif
-    a.wx = S.tile_wx;
-    a.fuse = S.fuse_finalize;
-    a.wt = S.wtiles;
-    for (int c = 0; c <= 8; ++c) a.wo[c] = S.woff[0][c];
-    a.tq = S.tq + (round & 1) * 8 * TQ_STRIDE;
-    a.tq_next = S.tq + ((round + 1) & 1) * 8 * TQ_STRIDE;
-    return a;
-}
-
-// First plane (relative to the slab's) of region h of NR equal regions over nx planes.  (A last
-// region half the size of the others measured within noise, profiles/r05/rejected/rlast.txt.)
-uint32_t region_plane(uint32_t nx, int NR, int h) {
-    if (h >= NR) return nx;
-    return (uint32_t)((uint64_t)nx * h / NR);
-}
-
-// Region h of NR of a plane-aligned slab: planes [x0 + region_plane(h), x0 + region_plane(h + 1)),
-// whose tiles (relative to lo / TILE) are [rb[h], rb[h + 1]) -- a tile belongs to the plane it
-// starts in (the slab's first tile to the first plane).  False if the slab is not plane-aligned.
-bool region_tiles(uint32_t lo, uint32_t nloc, uint64_t g2, int NR, uint32_t* rb) {
-    if (!g2 || nloc % g2 || lo % g2 || NR < 1) return false;
-    const uint32_t tb = lo / TILE;
-    const uint32_t tend = (uint32_t)(((uint64_t)lo + nloc + TILE - 1) / TILE);
-    const uint32_t x0 = (uint32_t)(lo / g2), nx = (uint32_t)(nloc / g2);
-    for (int h = 0; h <= NR; ++h) {
-        const uint64_t x = x0 + region_plane(nx, NR, h);
-        rb[h] = (x <= x0 ? tb : (uint32_t)std::min<uint64_t>((x * g2 + TILE - 1) / TILE, tend)) - tb;
-    }
-    return true;
-}
-
-// Walk 3's visiting order (host, at create): walk 2's items (TileWalk) for each
-// of the 8 XCDs, empty items dropped -- every tile of the slab exactly once.
-// list: tiles relative to lo / TILE; woff[0][c]..woff[0][c + 1]: XCD c's items.
-// NR > 1 (launch_round_regions): the planes of region h (region_tiles) dealt to the
-// 8 XCDs in the same way, XCD c's items at woff[h][c]..woff[h][c + 1].
-bool build_walk_list(const DevState& S, int NR, std::vector<uint32_t>& list, uint32_t woff[][9]) {
-    const uint64_t g2 = S.G.g2;
-    if (!g2 || S.nloc % g2 || S.lo % g2 || NR < 1 || NR > RREG_MAX) return false;
-    const uint32_t tb = S.lo / TILE;
-    const uint32_t tend = (uint32_t)(((uint64_t)S.lo + S.nloc + TILE - 1) / TILE);
-    const uint32_t x0 = (uint32_t)(S.lo / g2), nx = (uint32_t)(S.nloc / g2);
-    const uint32_t kp = (uint32_t)((g2 + TILE - 1) / TILE + 1);
-    auto first = [&](uint32_t x) -> uint32_t {
-        return x <= x0 ? tb : (uint32_t)std::min<uint64_t>((x * g2 + TILE - 1) / TILE, tend);
-    };
-    list.clear();
-    for (int h = 0; h < NR; ++h) {
-        const uint32_t r0 = x0 + region_plane(nx, NR, h);
-        const uint32_t nr = x0 + region_plane(nx, NR, h + 1) - r0;
-        for (uint32_t c = 0; c < 8; ++c) {
-            woff[h][c] = (uint32_t)list.size();
-            const uint32_t xa = r0 + (uint32_t)((uint64_t)nr * c / 8);
-            const uint32_t nxa = r0 + (uint32_t)((uint64_t)nr * (c + 1) / 8) - xa;
-            uint32_t nwin = S.tile_wx ? (nxa + S.tile_wx - 1) / S.tile_wx : 1u;
-            if (nwin == 0) nwin = 1;
-            for (uint32_t v = 0; v < nwin && nxa; ++v) {
-                const uint32_t xs = (uint32_t)((uint64_t)nxa * v / nwin), xe = (uint32_t)((uint64_t)nxa * (v + 1) / nwin);
-                for (uint32_t k = 0; k < kp; ++k)
-                    for (uint32_t x = xa + xs; x < xa + xe; ++x) {
-                        const uint32_t ti = first(x) + k;
-                        if (ti < first(x + 1)) list.push_back(ti - tb);
-                    }
-            }
-        }
-        woff[h][8] = (uint32_t)list.size();
-    }
-    return list.size() == (size_t)(tend - tb);
-}
-
-// Resident 256-thread blocks of the push-sum tile kernel on this device (walk 3
-// runs exactly that grid); 0 if unknown.
+// Resident blocks of the push-sum tile kernel on this device (walk 3 runs exactly
+// that grid); 0 if unknown.
 int ps_tile_resident_blocks(int topo, bool remote, int device) {
-    const void* f = topo == LINE     ? reinterpret_cast<const void*>(&k_ps_tile<LINE, false>)
-                    : topo == GRID3D ? reinterpret_cast<const void*>(&k_ps_tile<GRID3D, false>)
-                    : remote         ? reinterpret_cast<const void*>(&k_ps_tile<IMP3D, true>)
-                                     : reinterpret_cast<const void*>(&k_ps_tile<IMP3D, false>);
+    const PsTileKernel f = ps_tile_kernel(topo, remote);
     int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, TPB, 0) != hipSuccess) return 0;
+    if (!f) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(f), TPB, 0) != hipSuccess)
+        return 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
     return per_cu * cus;
 }
 
+// The push-sum half of launch_round_tile (gp_tile_host.hip).
+hipError_t launch_ps_tile(const DevState& S, const RoundArgs& a, uint32_t round, int grid, hipStream_t st) {
+    const PsTileKernel f = ps_tile_kernel(S.topo, S.rk != nullptr);
+    if (!f || (S.topo == IMP3D && !S.ind4)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(f, dim3(grid), dim3(TPB), 0, st, a, round);
+    return hipGetLastError();
+}
+
+#ifdef GP_TILE_WIDE
+}  // namespace wide
+#else
 // Launch h of round `round` when the round kernel runs region by region (DevState::rregions;
 // Imp3D push-sum across ranks): region h's tiles, its own pair of queue counters by launch parity.
 hipError_t launch_round_tile_region(const DevState& S, uint32_t round, uint32_t h, int grid, hipStream_t st) {
@@ -1395,90 +905,5 @@ hipError_t launch_round_tile_region(const DevState& S, uint32_t round, uint32_t 
     hipLaunchKernelGGL((k_ps_tile<IMP3D, true>), dim3(grid), dim3(TPB), 0, st, a, round);
     return hipGetLastError();
 }
-
-hipError_t launch_round_tile(const DevState& S, uint32_t round, int grid, hipStream_t st) {
-    if (S.rregions > 1) return hipErrorInvalidValue;  // launch_round_tile_region per region
-    const RoundArgs a = make_round_args(S, round);
-    const dim3 g(grid), b(TPB);
-    // Imp3D slabs of a multi-rank run (push-sum: received lists; gossip: tagged slots)
-    const bool remote = S.alg == PUSHSUM ? S.rk != nullptr : S.rtag != nullptr;
-    if (S.alg == PUSHSUM && S.topo == IMP3D && !S.ind4) return hipErrorInvalidValue;
-    if (S.alg == PUSHSUM) {
-        switch (S.topo) {
-            case LINE: hipLaunchKernelGGL((k_ps_tile<LINE, false>), g, b, 0, st, a, round); break;
-            case GRID3D: hipLaunchKernelGGL((k_ps_tile<GRID3D, false>), g, b, 0, st, a, round); break;
-            default:
-                if (remote) hipLaunchKernelGGL((k_ps_tile<IMP3D, true>), g, b, 0, st, a, round);
-                else hipLaunchKernelGGL((k_ps_tile<IMP3D, false>), g, b, 0, st, a, round);
-                break;
-        }
-    } else {
-        switch (S.topo) {
-            case LINE: hipLaunchKernelGGL((k_gossip_tile<LINE, false>), g, b, 0, st, a, round); break;
-            case GRID3D: hipLaunchKernelGGL((k_gossip_tile<GRID3D, false>), g, b, 0, st, a, round); break;
-            default:
-                if (remote) hipLaunchKernelGGL((k_gossip_tile<IMP3D, true>), g, b, 0, st, a, round);
-                else hipLaunchKernelGGL((k_gossip_tile<IMP3D, false>), g, b, 0, st, a, round);
-                break;
-        }
-    }
-    return hipGetLastError();
-}
-
-// Imp3D push-sum senders with their degree packed in the top two bits
-// (deg - 4 in [0, 3]; every node has 3..6 lattice slots + the random one when
-// g >= 2), so the tile kernel's in-edge pass needs no division to find it.
-// Valid when every id fits 30 bits (P <= 2^30).
-__global__ __launch_bounds__(TPB) void k_pack_src_deg(const uint32_t* src, uint32_t* out, uint32_t n, Geom G) {
-    for (uint32_t e = blockIdx.x * TPB + threadIdx.x; e < n; e += gridDim.x * TPB) {
-        const uint32_t i = src[e];
-        const uint32_t deg = popc6(present_mask<IMP3D>(i, G)) + 1u;
-        out[e] = i | ((deg - 4u) << 30);
-    }
-}
-
-hipError_t launch_pack_src_deg(const uint32_t* src, uint32_t* out, uint32_t n, const Geom& G, int grid,
-                               hipStream_t st) {
-    hipLaunchKernelGGL(k_pack_src_deg, dim3(grid), dim3(TPB), 0, st, src, out, n, G);
-    return hipGetLastError();
-}
-
-// Nibble in-degrees of the slab's tiles (DevState::ind4) from in_off.
-// wide_at: in-degrees from this value on are stored as 15, the "read in_off"
-// mark (15 in the product; tests lower it to exercise that path).
-__global__ __launch_bounds__(TPB) void k_pack_ind4(const uint32_t* __restrict__ in_off, uint32_t lo, uint32_t nloc,
-                                                   uint32_t j00, uint8_t* __restrict__ out, uint32_t nbytes,
-                                                   uint32_t wide_at) {
-    for (uint32_t b = blockIdx.x * TPB + threadIdx.x; b < nbytes; b += gridDim.x * TPB) {
-        uint32_t v = 0;
-#pragma unroll
-        for (uint32_t h = 0; h < 2; ++h) {
-            const uint32_t j = j00 + 2 * b + h;
-            if (j - lo < nloc) {
-                const uint32_t d = in_off[j + 1] - in_off[j];
-                v |= (d >= wide_at ? 15u : d) << (4 * h);
-            }
-        }
-        out[b] = (uint8_t)v;
-    }
-}
-
-uint32_t ind4_bytes_for(uint32_t lo, uint32_t nloc) { return tiles_for(lo, nloc) * (TILE / 2) + 16u; }
-
-hipError_t launch_pack_ind4(const DevState& S, uint32_t wide_at, int grid, hipStream_t st) {
-    const uint32_t nbytes = tiles_for(S.lo, S.nloc) * (TILE / 2);
-    hipLaunchKernelGGL(k_pack_ind4, dim3(grid), dim3(TPB), 0, st, S.in_off - S.lo, S.lo, S.nloc, (S.lo / TILE) * TILE,
-                       S.ind4, nbytes, std::min(wide_at, 15u));
-    return hipGetLastError();
-}
-
-hipError_t launch_rbits_init(const DevState& S, int grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_rbits_init, dim3(grid), dim3(TPB), 0, st, S.nb[0] - S.base, S.rbits[0], S.lo, S.nloc,
-                       S.rbits_words);
-    return hipGetLastError();
-}
-
-#ifdef GP_ROUND_WIDE
-}  // namespace wide
 #endif
 }  // namespace gp

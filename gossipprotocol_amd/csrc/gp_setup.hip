@@ -576,7 +576,7 @@ int build_imp3d(gp_sim* s) {
         S.ind4 = nullptr;
         if (S.alg == PUSHSUM && S.kernel == KERNEL_TILE) {
             if ((rc = dev_alloc_t(s, &S.ind4, ind4_bytes_for(S.lo, S.nloc)))) return rc;
-            uint32_t wide_at = 15;  // in-degree >= 15: the tile reads in_off (gp_round.hip)
+            uint32_t wide_at = 15;  // in-degree >= 15: the tile reads in_off (gp_ps_tile.hip)
             if (const char* e = exp_env("GP_IND4_WIDE")) wide_at = (uint32_t)std::max(1, std::atoi(e));
             HIP_TRY(launch_pack_ind4(S, wide_at, s->grid, s->stream));
         }
@@ -883,7 +883,7 @@ void choose_kernel(gp_sim* s, int64_t nloc_max, int& kernel, uint32_t& col_xsegs
     if (const char* e = exp_env("GP_WX")) wx = (uint32_t)std::max(1, std::atoi(e));
     // size class of the tiled kernels: line / 3D push-sum on a slab with at most two tiles per
     // resident block of the 4-nodes-per-thread kernel (~2500 tiles, P <~ 2.6e6 per slab) runs the
-    // 1024-thread, one-node-per-thread build (gp_round_wide.hip): its node phase is one memory
+    // 1024-thread, one-node-per-thread build (gp_ps_tile_wide.hip): its node phase is one memory
     // round trip per tile instead of four, which is what bounds a round with few tiles per block
     // (C2, 3D push-sum P = 1e6: 26.5 -> 20.7 us per round; line push-sum n = 1000: 10.2 -> 8.8).
     // Imp3D push-sum (its in-edge pass spills at 8 waves) and the gossip tile kernel measured

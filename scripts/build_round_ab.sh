@@ -1,11 +1,11 @@
 #!/bin/bash
-# Same-box A/B libraries: one source (SRC, default gp_round) at a git revision, the working tree
+# Same-box A/B libraries: one source (SRC, default gp_ps_tile) at a git revision, the working tree
 # or a file, compiled into the experiments build (+ EXTRA flags) and linked with the experiments
 # objects of the other sources.
 #   [SRC=gp_col] [EXTRA=...] scripts/build_round_ab.sh <name> <rev|WORKTREE|file.hip>  ->  build/ablate/lib_<name>.so
 set -e
 cd "$(dirname "$0")/.."
-name=$1; rev=$2; S=${SRC:-gp_round}
+name=$1; rev=$2; S=${SRC:-gp_ps_tile}
 make -s -C gossipprotocol_amd/csrc >/dev/null
 mkdir -p build/ablate/src
 src=build/ablate/src/${S}_$name.hip

@@ -138,7 +138,7 @@ XTILE = 1024  # the lists' tiles: 1024 ids on global multiples (the push-sum til
 
 def region_tiles(lo, nloc, g2, NH, nt):
     """Tile boundaries (relative to lo // XTILE) of the NH exchange regions of a slab
-    (gp_round.hip region_tiles): region h holds the planes [x0 + nx h / NH, x0 + nx (h + 1) / NH),
+    (gp_tile_host.hip region_tiles): region h holds the planes [x0 + nx h / NH, x0 + nx (h + 1) / NH),
     a tile belonging to the plane it starts in; a slab not made of whole planes is cut
     into equal tile counts."""
     if not g2 or nloc % g2 or lo % g2:

@@ -1,4 +1,4 @@
-"""GPU: the push-sum tile kernel's two per-tile bodies (gp_round.hip, ps_tiles) against the CPU
+"""GPU: the push-sum tile kernel's two per-tile bodies (gp_ps_tile.hip, ps_tiles) against the CPU
 oracle, bit-exact.
 
 A tile that lies wholly inside the slab and (Imp3D) is staged and not `wide` runs the FULL body

@@ -26,7 +26,7 @@ condition is asserted, never relaxed: a case that misses it gets more rounds or 
 (Seed 3 serves all but Imp3D g = 66, where it strands a node whose neighbours all converged
 first: only the injector reaches it, one pick per round among 287 496 -- hence SEED.)
 
-Tile kernel (k_gossip_tile, gp_round.hip; GP_KERNEL=tile): the tile-edge sizes that
+Tile kernel (k_gossip_tile, gp_gossip_tile.hip; GP_KERNEL=tile): the tile-edge sizes that
 test_gpu_fulltile.py justifies for push-sum (all tiles full, one full + one partial, a single
 partial tile, a last wave that is partial), the line at P = 1024, 1025, 2048, and the unstaged
 in-edge path, which no tile reaches by itself (more than SRC_CAP = 1536 in-edges against a mean

@@ -346,7 +346,7 @@ def test_kernel_variant_parity(kernel, n, topo, alg, seed, rounds, chk, xsegs, m
     GP_KERNEL) bit-exact vs the oracle, the column march also with its
     x-segmentation forced; the tiled kernel in the size class its population
     selects (tile), forced to 256 threads x 4 nodes (tile4, GP_WIDE=0) and to the
-    1024-thread x 1 node build (tile1, GP_WIDE=1, gp_round_wide.hip)."""
+    1024-thread x 1 node build (tile1, GP_WIDE=1, gp_ps_tile_wide.hip)."""
     if kernel == "col" and alg == "push-sum":
         pytest.skip("the column march runs lattice gossip only")
     if kernel == "tile1" and (alg != "push-sum" or topo == "Imp3D"):

@@ -10,7 +10,7 @@
 // and divide the per-dispatch counter by the bytes printed here
 // (tools/calib_summary.py).
 //
-// Shapes (as the tile kernel issues them, gp_round.hip):
+// Shapes (as the tile kernel issues them, gp_ps_tile.hip):
 //   rd16       16 B per lane, lane-contiguous global_load_dwordx4 (own (s, w))
 //   rd16_nt    the same, non-temporal
 //   rd4_nt     4 B per lane, non-temporal global_load_dword (in-list senders)

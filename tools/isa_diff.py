@@ -1,7 +1,7 @@
 """Compare the gfx950 instructions of kernels between two device-assembly dumps.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off \
-          --offload-device-only -S gp_round.hip -o before.s
+          --offload-device-only -S gp_ps_tile.hip -o before.s
     ... edit ...
     python tools/isa_diff.py before.s after.s [kernel-substring ...]
 
