@@ -151,7 +151,10 @@ int alloc_slab(gp_sim* s, Slab& sl, int r) {
         const FullBinPlan fp = full_bin_plan(S.nloc, W == 1);
         S.fb_nb2 = fp.nb2;
         S.fb_cap2 = fp.cap2;
-        const size_t m2 = (size_t)fp.nb2 * fp.cap2;
+        // (GP_FB_CAP2 / GP_FB_CAP1, experiments: smaller bins, to put a round's fullest fine tile /
+        // coarse bin exactly at and one past its capacity; tests/test_gpu_fullbin_edges.py)
+        if (const char* e = exp_env("GP_FB_CAP2")) S.fb_cap2 = std::min<uint32_t>(FB_CAP2, (uint32_t)std::max(1, std::atoi(e)));
+        const size_t m2 = (size_t)fp.nb2 * S.fb_cap2;
         if ((rc = dev_alloc_t(s, &S.fb_cnt2, fp.nb2)) || (rc = dev_alloc_t(s, &S.fb_hdr2, m2)) ||
             (rc = dev_alloc_t(s, &S.fb_pay2, m2)))
             return rc;
@@ -164,8 +167,9 @@ int alloc_slab(gp_sim* s, Slab& sl, int r) {
             S.fb_s1 = f1.s1;
             S.fb_nb1 = f1.nb1;
             S.fb_cap1 = f1.cap1;
+            if (const char* e = exp_env("GP_FB_CAP1")) S.fb_cap1 = std::min<uint32_t>(f1.cap1, (uint32_t)std::max(1, std::atoi(e)));
             S.fb_fused = fused && f1.nb1 <= full_bin_fused_max_bins() ? 1u : 0u;
-            const size_t m1 = (size_t)f1.nb1 * f1.cap1;
+            const size_t m1 = (size_t)f1.nb1 * S.fb_cap1;
             // (+ FB_JUNK: the fold's write-out sends lanes without a message to the slots past the
             // last bin, so every thread issues the same number of stores)
             if ((rc = dev_alloc_t(s, &S.fb_cnt1, f1.nb1)) || (rc = dev_alloc_t(s, &S.fb_hdr1, m1 + FB_JUNK)) ||

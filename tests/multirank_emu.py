@@ -36,6 +36,8 @@ oracle/srs_py.py (itself pinned by the Random123 known-answer vectors).
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
@@ -243,6 +245,26 @@ def full_capacity(na, nb, P):
 
 FB_TB = 12       # gp_fullbin.hpp: fine tiles of 4096 receivers
 FBM_KEYS = 192   # gp_fullbin.hip: keys of all ranks' coarse bins together, at most
+
+
+def full_bin_plan(nrecv, fused=False):
+    """gp_fullbin.hip full_bin_plan: coarse bins of 2^s1 receivers, fine tiles of 4096; the
+    fused fold (one rank) takes coarse bins one size smaller, at most 1024 of them."""
+    fb_tb, cap2 = 12, 4992
+    bits = 1
+    while bits < 32 and (1 << bits) < nrecv:
+        bits += 1
+    s1 = max((bits + fb_tb + 1) // 2 - (1 if fused else 0), fb_tb)
+    while (nrecv >> s1) >= 4096:
+        s1 += 1
+    while fused and ((nrecv + (1 << s1) - 1) >> s1) > 1024:
+        s1 += 1
+    while s1 - fb_tb > 12:
+        s1 -= 1
+    nb1 = (nrecv + (1 << s1) - 1) >> s1
+    nb2 = (nrecv + (1 << fb_tb) - 1) >> fb_tb
+    m1 = (1 << s1) * (nrecv / max(nrecv - 1, 1))
+    return nb1, int(m1 + 12.0 * math.sqrt(m1) + 1024.0), nb2, cap2
 
 
 def full_bin_multi_s1(bounds):

@@ -109,7 +109,7 @@ def test_product_library_has_no_environment_switches():
     exp = open(os.path.join(os.path.dirname(L.LIB_PATH), "libgossip_hip_exp.so"), "rb").read()
     for knob in (b"GP_KERNEL", b"GP_XSEGS", b"GP_WALK", b"GP_WX", b"GP_STAGE_CAP", b"GP_NO_PACK",
                  b"GP_FORCE_RCCL", b"GP_XCAP", b"GP_WIDE", b"GP_RQ8", b"GP_CHECK_CLOSE", b"GP_FUSE",
-                 b"GP_RREGIONS", b"GP_FB_FUSED", b"GP_IND4_WIDE"):
+                 b"GP_RREGIONS", b"GP_FB_FUSED", b"GP_IND4_WIDE", b"GP_FB_CAP1", b"GP_FB_CAP2"):
         assert knob not in prod, knob
         assert knob in exp, knob
     # overrides of variants measured and rejected are gone from both builds (round 6)

@@ -18,7 +18,7 @@ import pytest
 import numpy as np
 
 from tests.multirank_emu import (DIR_RANDOM, Geometry, S_PUSHSUM, S_TOPO, full_bin_multi_cap, full_bin_multi_s1,
-                                 full_region, resolve, slab_bounds, uniform)
+                                 full_bin_plan, full_region, resolve, slab_bounds, uniform)
 
 HBM_BYTES = 288e9
 GAUSS_12SIGMA_TAIL = 1.8e-33  # P(Z > 12)
@@ -103,26 +103,6 @@ def test_c5_imp3d_pushsum_1e9_world8_plan():
         assert steady < 0.1 * HBM_BYTES
     # a convergence run of 10^5 rounds x 56 pairs stays far from an overflow
     assert 1e5 * W * (W - 1) * GAUSS_12SIGMA_TAIL < 1e-25
-
-
-def full_bin_plan(nrecv, fused=False):
-    """gp_fullbin.hip full_bin_plan: coarse bins of 2^s1 receivers, fine tiles of 4096; the
-    fused fold (one rank) takes coarse bins one size smaller, at most 1024 of them."""
-    fb_tb, cap2 = 12, 4992
-    bits = 1
-    while bits < 32 and (1 << bits) < nrecv:
-        bits += 1
-    s1 = max((bits + fb_tb + 1) // 2 - (1 if fused else 0), fb_tb)
-    while (nrecv >> s1) >= 4096:
-        s1 += 1
-    while fused and ((nrecv + (1 << s1) - 1) >> s1) > 1024:
-        s1 += 1
-    while s1 - fb_tb > 12:
-        s1 -= 1
-    nb1 = (nrecv + (1 << s1) - 1) >> s1
-    nb2 = (nrecv + (1 << fb_tb) - 1) >> fb_tb
-    m1 = (1 << s1) * (nrecv / max(nrecv - 1, 1))
-    return nb1, int(m1 + 12.0 * math.sqrt(m1) + 1024.0), nb2, cap2
 
 
 def fb_bins_bytes(nb, cap):
