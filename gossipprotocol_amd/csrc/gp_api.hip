@@ -1,7 +1,7 @@
 // gp_api.hip -- C-ABI of libgossip_hip.so (include/gossip_hip.h): argument checks, the
 // calling thread's error slot, and the gp_step batch loop.  The host side behind it:
-// gp_setup.hip (everything before round 0) and gp_exchange.hip (one round across ranks),
-// sharing gp_host.hpp.
+// gp_setup.hip, gp_topology.hip and gp_xlayout.hip (everything before round 0) and
+// gp_exchange.hip (one round across ranks), sharing gp_host.hpp.
 //
 // Replaces, in /root/reference/Project2/Program.fs:
 //   * actor population + topology build (Program.fs:169-176,180-191,209-216,238-261)

@@ -12,7 +12,7 @@
 #include "gp_host.hpp"
 
 // Every inter-rank transfer of a round, described once per slab from its layout tables
-// (alloc_slab, setup_exchange, setup_halo, build_lists, build_bits): Slab::xhalo[b] the halo
+// (alloc_slab, setup_exchange, setup_halo, build_lists, build_bits; gp_plan.hpp): Slab::xhalo[b] the halo
 // planes and Slab::xplan[b][h] region h's messages of the round whose state lies in buffers b
 // (the pointers depend on the round through its parity only), in the order they are issued:
 //   1. the halo node bytes, lower neighbour then upper;
@@ -45,7 +45,7 @@ void build_transfers(gp_sim* s) {
                 add(halo, true, p, HS ? sl.hsend[k] : S.sw[b] + out, sw_bytes);
                 add(halo, false, p, HS ? sl.hrecv[k] : S.sw[b] + in, sw_bytes);
             }
-            uint8_t* xr = sl.xrecv + (size_t)b * sl.xr_stride;  // lists: this round parity's receive buffer
+            uint8_t* xr = sl.xrecv + (size_t)b * sl.xl.xr_stride;  // lists: this round parity's receive buffer
             sl.xplan[b].assign(NH, {});
             for (int h = 0; h < NH; ++h)
                 for (int p = 0; p < W; ++p) {
@@ -53,16 +53,16 @@ void build_transfers(gp_sim* s) {
                     std::vector<Xfer>& v = sl.xplan[b][h];
                     const size_t i = (size_t)h * W + p;
                     if (sl.bits) {  // the bitmap chunks, each way
-                        add(v, true, p, S.sbits + sl.bo[p] / 32, (size_t)(sl.bn[p] + 31) / 32 * 4);
-                        add(v, false, p, sl.rbits_in + sl.ro[p] / 32, (size_t)(sl.rn[p] + 31) / 32 * 4);
+                        add(v, true, p, S.sbits + sl.bl.bo[p] / 32, (size_t)(sl.bl.bn[p] + 31) / 32 * 4);
+                        add(v, false, p, sl.rbits_in + sl.bl.ro[p] / 32, (size_t)(sl.bl.rn[p] + 31) / 32 * 4);
                     } else if (sl.lists) {  // header words, then messages, each way
-                        add(v, true, p, sl.xsend + sl.lhdr[i], (size_t)s->list_nw[((size_t)r * NH + h) * W + p] * 16);
-                        add(v, true, p, sl.xsend + sl.lval[i], (size_t)sl.cap_out[i] * 16);
-                        add(v, false, p, xr + sl.rhdr[i], (size_t)s->list_nw[((size_t)p * NH + h) * W + r] * 16);
-                        add(v, false, p, xr + sl.rval[i], (size_t)sl.cap_in[i] * 16);
-                    } else if (!sl.sbytes.empty()) {  // slot buffers (gossip) / coarse bins (full push-sum)
-                        add(v, true, p, sl.xsend + sl.soff[i], sl.sbytes[i]);
-                        add(v, false, p, sl.xrecv + sl.roff[i], sl.rbytes[i]);
+                        add(v, true, p, sl.xsend + sl.xl.lhdr[i], (size_t)s->list_nw[((size_t)r * NH + h) * W + p] * 16);
+                        add(v, true, p, sl.xsend + sl.xl.lval[i], (size_t)sl.xl.cap_out[i] * 16);
+                        add(v, false, p, xr + sl.xl.rhdr[i], (size_t)s->list_nw[((size_t)p * NH + h) * W + r] * 16);
+                        add(v, false, p, xr + sl.xl.rval[i], (size_t)sl.xl.cap_in[i] * 16);
+                    } else if (!sl.xl.sbytes.empty()) {  // slot buffers (gossip) / coarse bins (full push-sum)
+                        add(v, true, p, sl.xsend + sl.xl.soff[i], sl.xl.sbytes[i]);
+                        add(v, false, p, sl.xrecv + sl.xl.roff[i], sl.xl.rbytes[i]);
                     }
                 }
         }
@@ -75,8 +75,8 @@ XPeer xpeer(uint8_t* buf, size_t off, uint32_t cap) {
     if (!cap) return p;
     uint8_t* b = buf + off;
     p.cnt = reinterpret_cast<uint32_t*>(b);
-    p.slots = reinterpret_cast<uint32_t*>(b + 16);
-    p.vals = reinterpret_cast<double2*>(b + 16 + (((size_t)cap * 4 + 15) & ~(size_t)15));
+    p.slots = reinterpret_cast<uint32_t*>(b + XBUF_SLOTS_OFF);
+    p.vals = reinterpret_cast<double2*>(b + xbuf_vals_off(cap));
     p.cap = cap;
     return p;
 }
@@ -175,8 +175,8 @@ FullArgs make_full_args(gp_sim* s, Slab& sl, uint32_t round) {
     a.me = sl.rank;
     for (int w = 0; w <= s->world; ++w) a.bounds[w] = s->bounds[w];
     for (int p = 0; p < s->world; ++p) {
-        a.peer[p] = xpeer(sl.xsend, sl.soff[p], sl.cap_out[p]);
-        a.rpeer[p] = xpeer(sl.xrecv, sl.roff[p], sl.cap_in[p]);
+        a.peer[p] = xpeer(sl.xsend, sl.xl.soff[p], sl.xl.cap_out[p]);
+        a.rpeer[p] = xpeer(sl.xrecv, sl.xl.roff[p], sl.xl.cap_in[p]);
     }
     return a;
 }
@@ -188,8 +188,8 @@ FullArgs make_full_args(gp_sim* s, Slab& sl, uint32_t round) {
 // This rank's own share of region h's bins, round parity `par` (Slab::xown).
 FbBins own_bins(gp_sim* s, Slab& sl, int h, uint32_t par) {
     const size_t i = (size_t)h * s->world + sl.rank;
-    uint8_t* base = par & 1u ? sl.xown + sl.ooff[h] : sl.xrecv + sl.roff[i];
-    return fb_bins_at(base, sl.S.fb_nb1, sl.cap_in[i]);
+    uint8_t* base = par & 1u ? sl.xown + sl.xl.ooff[h] : sl.xrecv + sl.xl.roff[i];
+    return fb_bins_at(base, sl.S.fb_nb1, sl.xl.cap_in[i]);
 }
 
 // send_pass: round 0's send pass fills this round's own bins (the fold fills the next round's).
@@ -225,10 +225,10 @@ FullBinArgs make_fullbin_args(gp_sim* s, Slab& sl, uint32_t round, int h, bool s
     a.in_item0[0] = 0;
     for (int p = 0; p < W; ++p) {
         const size_t i = (size_t)h * W + p;
-        a.in[p] = p == sl.rank ? own_bins(s, sl, h, round) : fb_bins_at(sl.xrecv + sl.roff[i], S.fb_nb1, sl.cap_in[i]);
+        a.in[p] = p == sl.rank ? own_bins(s, sl, h, round) : fb_bins_at(sl.xrecv + sl.xl.roff[i], S.fb_nb1, sl.xl.cap_in[i]);
         a.out[p] = p == sl.rank ? own_bins(s, sl, h, send_pass ? round : round + 1)
-                                : fb_bins_at(sl.xsend + sl.soff[i], full_coarse_bins(s->bounds, p, S.fb_s1), sl.cap_out[i]);
-        a.in_item0[p + 1] = a.in_item0[p] + (sl.cap_in[i] ? S.fb_nb1 * ((sl.cap_in[i] + item - 1) / item) : 0u);
+                                : fb_bins_at(sl.xsend + sl.xl.soff[i], full_coarse_bins(s->bounds, p, S.fb_s1), sl.xl.cap_out[i]);
+        a.in_item0[p + 1] = a.in_item0[p] + (sl.xl.cap_in[i] ? S.fb_nb1 * ((sl.xl.cap_in[i] + item - 1) / item) : 0u);
     }
     return a;
 }
@@ -263,14 +263,21 @@ int launch_round_full_multi(gp_sim* s, uint32_t r, hipEvent_t e0, hipEvent_t e1)
         // (their last transfer is done: finalize waited for it), the own next-round bins' (the
         // split of round r - 1 read them); round 0 also this round's own bins, for the send pass
         // (zero_send: the send bins alone -- round 0's send pass has used them once already)
+        // at most: the fine tiles', and per region (NH = FB_REGIONS, exchange_regions) the bins to
+        // each of W <= XMAXW ranks and the own bins of this parity
+        static_assert(ZeroList::MAX >= 1 + FB_REGIONS * (XMAXW + 1), "a round's counter arrays fit the ZeroList");
         auto zero_counts = [&](bool zero_send) -> int {
             for (Slab& sl : s->slab) {
                 ZeroList z{};
+                bool fits = true;
                 auto add = [&](uint32_t* p, uint32_t n) {
-                    if (p && n && z.k < ZeroList::MAX) {
-                        z.p[z.k] = p;
-                        z.n[z.k++] = n;
+                    if (!p || !n) return;
+                    if (z.k == ZeroList::MAX) {
+                        fits = false;
+                        return;
                     }
+                    z.p[z.k] = p;
+                    z.n[z.k++] = n;
                 };
                 if (!zero_send) add(sl.S.fb_cnt2, sl.S.fb_nb2);
                 for (int h = 0; h < NH; ++h) {
@@ -278,6 +285,10 @@ int launch_round_full_multi(gp_sim* s, uint32_t r, hipEvent_t e0, hipEvent_t e1)
                     for (int p = 0; p < s->world; ++p)
                         if (p != sl.rank || !zero_send) add(a.out[p].cnt, a.out[p].nb);  // (own: next parity)
                     if (r == 0 && !zero_send) add(a.in[sl.rank].cnt, a.in[sl.rank].nb);
+                }
+                if (!fits) {
+                    set_err("internal: more than %d counter arrays to clear per round", ZeroList::MAX);
+                    return GP_EINVAL;
                 }
                 HIP_TRY(launch_zero_list(z, s->stream));
             }
@@ -390,11 +401,11 @@ int exchange_region(gp_sim* s, uint32_t rn, int h, int hg, hipStream_t cs) {
                 for (int d = 0; d < W; ++d) {
                     if (d == sl.rank) continue;
                     const size_t i = (size_t)h * W + d;
-                    la.peer[d].hdr = reinterpret_cast<XHdr*>(sl.xsend + sl.lhdr[i]);
-                    la.peer[d].vals = reinterpret_cast<double2*>(sl.xsend + sl.lval[i]);
+                    la.peer[d].hdr = reinterpret_cast<XHdr*>(sl.xsend + sl.xl.lhdr[i]);
+                    la.peer[d].vals = reinterpret_cast<double2*>(sl.xsend + sl.xl.lval[i]);
                     la.peer[d].cnt = sl.xcnt + i;
-                    la.peer[d].cap = sl.cap_out[i];
-                    la.peer[d].vbase = sl.vbase[i];
+                    la.peer[d].cap = sl.xl.cap_out[i];
+                    la.peer[d].vbase = sl.xl.vbase[i];
                 }
                 la.overflow = sl.overflow;
                 HIP_TRY(launch_list_pack(la, cs));
@@ -409,7 +420,7 @@ int exchange_region(gp_sim* s, uint32_t rn, int h, int hg, hipStream_t cs) {
             pa.xdst = sl.xdst;
             pa.lo = S.lo;
             pa.nloc = S.nloc;
-            xregion(sl, NH, h, pa.s_lo, pa.s_hi);
+            xregion(S.lo, S.nloc, sl.lists, sl.tb, NH, h, pa.s_lo, pa.s_hi);
             pa.base = S.base;
             pa.W = W;
             pa.me = sl.rank;
@@ -418,7 +429,7 @@ int exchange_region(gp_sim* s, uint32_t rn, int h, int hg, hipStream_t cs) {
             for (int w = 0; w <= W; ++w) pa.bounds[w] = s->bounds[w];
             for (int p = 0; p < W; ++p) {
                 const size_t i = (size_t)h * W + p;
-                pa.peer[p] = xpeer(sl.xsend, sl.soff[i], sl.cap_out[i]);
+                pa.peer[p] = xpeer(sl.xsend, sl.xl.soff[i], sl.xl.cap_out[i]);
                 z.cnt[p] = pa.peer[p].cnt;
             }
             z.n = W;
@@ -449,8 +460,8 @@ int exchange_close(gp_sim* s, uint32_t rn) {
         for (Slab& sl : s->slab) {
             // one rumour per received bit at its target, counted for round rn; then the send
             // bitmap is cleared for the next round kernel
-            HIP_TRY(launch_apply_bits(sl.rbits_in, sl.nbits_in / 32, sl.tgt, sl.S.rq[rn & 1], sl.S.rq8, s->stream));
-            if (sl.nbits_out) HIP_TRY(hipMemsetAsync(sl.S.sbits, 0, (size_t)sl.nbits_out / 8, s->stream));
+            HIP_TRY(launch_apply_bits(sl.rbits_in, sl.bl.nbits_in / 32, sl.tgt, sl.S.rq[rn & 1], sl.S.rq8, s->stream));
+            if (sl.bl.nbits_out) HIP_TRY(hipMemsetAsync(sl.S.sbits, 0, (size_t)sl.bl.nbits_out / 8, s->stream));
         }
     } else if (imp && !lists) {
         for (int h = 0; h < NH; ++h) {
@@ -467,7 +478,7 @@ int exchange_close(gp_sim* s, uint32_t rn) {
                 ua.push = push ? 1 : 0;
                 for (int p = 0; p < W; ++p) {
                     const size_t i = (size_t)h * W + p;
-                    ua.peer[p] = xpeer(sl.xrecv, sl.roff[i], sl.cap_in[i]);
+                    ua.peer[p] = xpeer(sl.xrecv, sl.xl.roff[i], sl.xl.cap_in[i]);
                 }
                 ua.overflow = sl.overflow;
                 ua.all_active = &sl.S.ctl->all_active;

@@ -40,7 +40,6 @@
 namespace gp {
 namespace {
 
-constexpr int FB_MAXBINS = 4096;                   // LDS counters of A and B
 // (No wave priority here: raised while the fold / split issue their loads and stores it measured
 // 3.17-3.18 against 3.03-3.17 ms/round, C4 same box, profiles/r04/setprio_c3c4.txt.)
 constexpr uint32_t FB_NONE = 0xFFFFu;
@@ -406,7 +405,7 @@ __global__ __launch_bounds__(FBR_THREADS, 1) void k_fb_split(FullBinArgs a, uint
 }
 
 // ---------------------------------------------------------------- several ranks
-// Contiguous id slabs (gp_setup.hip make_bounds); W <= XMAXW.  Every rank's coarse bins
+// Contiguous id slabs (gp_plan.hpp slab_bounds); W <= XMAXW.  Every rank's coarse bins
 // have the size 2^s1 (full_bin_multi_s1), so a message to target t has the LDS key
 // kb(b) + ((t - bounds[b]) >> s1), b = owner of t, kb(b) = the bins of the ranks below b:
 // key order = destination rank, then the destination's coarse bin.
@@ -419,8 +418,6 @@ __device__ __forceinline__ uint32_t multi_key(const FullBinArgs& a, uint32_t t) 
         }
     return kb + ((t - base) >> a.s1);
 }
-
-constexpr uint32_t FBF_MAXB1 = 1024;  // keys (coarse bins) the fold's send phase can bin into (LDS reservation slots)
 
 // A block's destination bins, in LDS: indexing the kernel arguments by a per-lane rank
 // would be a global load per message.
@@ -863,63 +860,13 @@ __global__ __launch_bounds__(FBF_THREADS) void k_fb_fold(FullBinArgs a, uint32_t
 }
 
 // ---------------------------------------------------------------- host side
-// Bins for the nrecv receivers of a rank (one rank: nrecv = P).
-FullBinPlan full_bin_plan(uint32_t P, bool fused) {
-    FullBinPlan p{};
-    uint32_t bits = 1;
-    while (bits < 32 && ((uint64_t)1 << bits) < P) ++bits;
-    // coarse bins ~ sqrt(P / TILE) so both passes write runs of ~10-20 messages;
-    // at most FB_MAXBINS coarse bins and FB_MAXBINS fine tiles per coarse bin.  The
-    // fused fold (one rank) takes coarse bins half that size: the split's runs get
-    // longer and the fold's shorter; P = 1e8, same box: rule 3.37, -1 3.26, -2 3.25,
-    // -3 3.38-3.40 ms/round (profiles/r04/c4_fused/s1_sweep.txt)
-    uint32_t s1 = (bits + FB_TB + 1) / 2 - (fused ? 1u : 0u);
-    if (s1 < FB_TB) s1 = FB_TB;
-    while (((uint64_t)P >> s1) >= FB_MAXBINS) ++s1;
-    while (fused && (((uint64_t)P + (1ull << s1) - 1) >> s1) > FBF_MAXB1) ++s1;
-    while (s1 - FB_TB > 12) --s1;
-    p.s1 = s1;
-    p.nb1 = (uint32_t)(((uint64_t)P + (1ull << s1) - 1) >> s1);
-    p.nb2 = (uint32_t)(((uint64_t)P + (1u << FB_TB) - 1) >> FB_TB);
-    const double m1 = (double)(1ull << s1) * ((double)P / (double)(P > 1 ? P - 1 : 1));
-    p.cap1 = (uint32_t)(m1 + 12.0 * std::sqrt(m1) + 1024.0);
-    p.cap2 = FB_CAP2;
-    return p;
-}
-
-// Several ranks: the smallest coarse-bin size (>= a fine tile) that keeps the keys of all ranks'
-// bins together at most FBM_KEYS -- about the one-rank fused fold's 191 bins at C4, whose runs
-// (~21 messages per (tile, key)) measured best there; larger bins also carry less 12-sigma
-// padding through the exchange (C4 at W = 8: 2^19 receivers, 24 bins per rank, +6.8 %).
-constexpr uint32_t FBM_KEYS = 192;
-uint32_t full_bin_multi_s1(const uint32_t* bounds, int W) {
-    uint32_t s1 = FB_TB;
-    for (;; ++s1) {
-        uint64_t keys = 0;
-        for (int b = 0; b < W; ++b) keys += ((uint64_t)(bounds[b + 1] - bounds[b]) + (1ull << s1) - 1) >> s1;
-        if (keys <= FBM_KEYS || s1 - FB_TB >= 12) break;
-    }
-    return s1;
-}
-
-uint32_t full_bin_multi_cap(uint32_t n, uint32_t s1, uint32_t P) {
-    const double m = (double)n * (double)(1ull << s1) / (double)(P > 1 ? P - 1 : 1);
-    return (uint32_t)std::min<double>(std::ceil(m + 12.0 * std::sqrt(m) + 64.0), (double)n);
-}
-
-size_t fb_bins_bytes(uint32_t nb, uint32_t cap) {
-    if (!nb || !cap) return 0;
-    const size_t c = ((size_t)nb * 4 + 15) & ~(size_t)15, h = ((size_t)nb * cap * 4 + 15) & ~(size_t)15;
-    return c + h + (size_t)nb * cap * 16;
-}
-
+// (The bins' plan -- full_bin_plan, full_bin_multi_s1 / _cap, fb_bins_bytes -- is gp_plan.hpp.)
 FbBins fb_bins_at(uint8_t* base, uint32_t nb, uint32_t cap) {
     FbBins f{};
     if (!nb || !cap) return f;
-    const size_t c = ((size_t)nb * 4 + 15) & ~(size_t)15, h = ((size_t)nb * cap * 4 + 15) & ~(size_t)15;
     f.cnt = reinterpret_cast<uint32_t*>(base);
-    f.hdr = reinterpret_cast<uint32_t*>(base + c);
-    f.pay = reinterpret_cast<double2*>(base + c + h);
+    f.hdr = reinterpret_cast<uint32_t*>(base + fb_bins_hdr_off(nb));
+    f.pay = reinterpret_cast<double2*>(base + fb_bins_pay_off(nb, cap));
     f.cap = cap;
     f.nb = nb;
     return f;

@@ -1,28 +1,11 @@
 // gp_fullbin.hpp -- full-topology push-sum rounds by two-level LDS binning
-// (gp_fullbin.hip).  Not part of the C-ABI.
+// (gp_fullbin.hip).  Not part of the C-ABI.  The bins' plan -- FB_* constants, FullBinPlan,
+// full_bin_plan, full_bin_multi_s1 / _cap, fb_bins_bytes -- is host arithmetic: gp_plan.hpp.
 #pragma once
 
 #include "gp_xchg.hpp"
 
 namespace gp {
-
-// fine tile = 2^FB_TB receivers (one fold block); 4096 (measured: 10 / 11 / 12 -> 3.65 / 3.63 /
-// 3.60 ms at P = 1e8)
-constexpr int FB_TB = 12;
-// messages per fine tile: expected 2^FB_TB + 12 sigma + 128 (4992 at 4096 receivers)
-constexpr int FB_CAP2 = ((1 << FB_TB) + 12 * (1 << (FB_TB / 2)) * (FB_TB % 2 ? 1414 : 1000) / 1000 + 128 + 63) / 64 * 64;
-
-// one rank: slots past the last coarse bin (hdr1 / pay1) that the fused fold's write-out sends
-// its lanes without a message to, so that every thread issues the same stores (k_fb_fold)
-constexpr size_t FB_JUNK = 64;
-
-struct FullBinPlan {
-    uint32_t s1;    // coarse bin = target >> s1
-    uint32_t nb1;   // coarse bins
-    uint32_t nb2;   // fine tiles
-    uint32_t cap1;  // message capacity per coarse bin
-    uint32_t cap2;  // message capacity per fine tile
-};
 
 // A set of `nb` coarse bins of `cap` messages each -- one rank's own coarse bins (cnt1 / hdr1 /
 // pay1), or, across ranks, the coarse bins of one destination rank's receivers that one exchange
@@ -36,7 +19,6 @@ struct FbBins {
     uint32_t cap;
     uint32_t nb;
 };
-size_t fb_bins_bytes(uint32_t nb, uint32_t cap);
 FbBins fb_bins_at(uint8_t* base, uint32_t nb, uint32_t cap);
 
 struct FullBinArgs {
@@ -70,13 +52,6 @@ struct FullBinArgs {
     uint32_t in_item0[XMAXW + 1];  // first split work item of each source rank
 };
 
-FullBinPlan full_bin_plan(uint32_t nrecv, bool fused);  // fused: one rank, the fold bins the next round
-// several ranks: the coarse-bin shift every rank uses (all slabs' bins together within the
-// fold's LDS reservation slots)
-uint32_t full_bin_multi_s1(const uint32_t* bounds, int W);
-// several ranks: the per-bin capacity of the messages a region of n senders sends to one
-// rank's coarse bin (Binomial(n, 2^s1 / (P - 1)) + 12 sigma + 64)
-uint32_t full_bin_multi_cap(uint32_t n_senders, uint32_t s1, uint32_t P);
 hipError_t launch_full_bin_round(const FullBinArgs& a, uint32_t round, int grid, hipStream_t st);
 // several ranks: round 0's messages (senders [s_lo, s_hi)) into the exchange buffers ...
 hipError_t launch_full_bin_send_multi(const FullBinArgs& a, uint32_t round, hipStream_t st);
@@ -84,9 +59,10 @@ hipError_t launch_full_bin_send_multi(const FullBinArgs& a, uint32_t round, hipS
 // region's send bins', this rank's own next-round bins': ZeroList), each region's received bins
 // split into this rank's fine tiles, and the fold of each region's tiles, which bins their
 // next-round messages into the region's exchange buffers
-constexpr int FB_REGIONS = 2;  // exchange regions of a slab (full push-sum)
 struct ZeroList {
-    static constexpr int MAX = 1 + FB_REGIONS * (XMAXW - 1) + 2 * FB_REGIONS;
+    // per slab and round: the fine tiles'; per region every rank's send bins' (the own share's
+    // next parity among them) and, in round 0, the own share's this parity (zero_counts, gp_exchange.hip)
+    static constexpr int MAX = 1 + FB_REGIONS * XMAXW + FB_REGIONS;
     uint32_t* p[MAX];
     uint32_t n[MAX];
     int k;

@@ -1,6 +1,8 @@
-// gp_host.hpp -- what the host units of libgossip_hip.so share: gp_setup.hip (before round 0),
-// gp_exchange.hip (one round across ranks), gp_api.hip (C ABI, gp_step batch loop) and, for the
-// error slot and device check, gp_ensemble_api.hip.  Hidden symbols: not the library's surface.
+// gp_host.hpp -- what the host units of libgossip_hip.so share: gp_setup.hip, gp_topology.hip and
+// gp_xlayout.hip (before round 0), gp_exchange.hip (one round across ranks), gp_api.hip (C ABI,
+// gp_step batch loop) and, for the error slot and device check, gp_ensemble_api.hip.  Hidden
+// symbols: not the library's surface.  What a run over several ranks allocates and addresses is
+// decided by gp_plan.hpp; these units carry it out.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -87,8 +89,7 @@ struct Slab {
     uint8_t* xsend = nullptr;
     uint8_t* xrecv = nullptr;
     uint32_t nedges = 0;
-    std::vector<uint32_t> cap_out, cap_in;           // [h * W + b]: region h of the buffer to / from rank b
-    std::vector<size_t> soff, sbytes, roff, rbytes;
+    XLayout xl;                        // capacities and byte layout of xsend / xrecv / xown (setup_exchange)
     unsigned int* overflow = nullptr;  // device flag
     // Imp3D push-sum over several ranks: sender-ordered lists (gp_xchg.hpp)
     bool lists = false;
@@ -98,23 +99,16 @@ struct Slab {
     uint16_t* xdr = nullptr;           // [id - lo]: d << 10 | rank in the tile's list for d (static)
     uint8_t* lwt = nullptr;            // [tile * (W + 1) + d]: the tile's LDS word layout in k_list_pack
     uint32_t* xcnt = nullptr;          // [h * W + d]: reservation counters of the send chunks
-    std::vector<size_t> lhdr, lval;    // send buffer: byte offsets of chunk (h, d)'s header words / slots
-    std::vector<size_t> rhdr, rval;    // receive buffer: byte offsets of chunk (h, p)'s header words / slots
-    size_t xr_stride = 0;              // the receive buffer of odd rounds at xrecv + xr_stride (region-by-region
-                                       // rounds: the next round's lists arrive during this one), else 0
-    std::vector<uint32_t> vbase;       // [h * W + d]: index of my chunk's first slot in d's vals region
     // full push-sum over several ranks: this rank's own share of region h's bins, by round parity:
     // parity 0 in xrecv (its receive region from itself), parity 1 in xown -- the fold of round r
     // fills parity r + 1 while the split of round r has read parity r, and a round's counters are
     // all cleared at its start (launch_round_full_multi)
     uint8_t* xown = nullptr;
-    size_t ooff[FB_REGIONS] = {};
     // Imp3D gossip (column kernel) over several ranks: random-edge sends as bitmaps (gp_xchg.hpp)
     bool bits = false;
     uint32_t* rbits_in = nullptr;      // receive bitmap: source a's chunk at bit ro[a]
     uint32_t* tgt = nullptr;           // local target of every receive-bitmap bit
-    uint32_t nbits_out = 0, nbits_in = 0;  // bitmap sizes (multiples of BITS_ALIGN)
-    std::vector<uint32_t> bo, bn, ro, rn;  // [peer]: chunk bit offset / bits, send and receive side
+    BitsLayout bl;                     // the chunks of the send and receive bitmaps (build_bits)
     // push-sum halo planes (3D / Imp3D, W > 1): the senders' (s, w) toward each neighbour, compacted
     // ([0]: lower neighbour, [1]: upper; k_halo_pack / k_halo_expand, gp_xchg.hpp)
     double2* hsend[2] = {nullptr, nullptr};
@@ -203,15 +197,19 @@ struct Scratch {
 // senders (rq) and cross ranks as counts; no bitmap, in-edge tags or slots.
 inline bool col_gossip_counts(const DevState& S) { return S.topo == IMP3D && S.alg == GOSSIP && S.kernel == KERNEL_COL; }
 
-// Coarse bins of rank p's receivers, 2^s1 each (full push-sum over several ranks, FbBins).
-inline uint32_t full_coarse_bins(const std::vector<uint32_t>& bounds, int p, uint32_t s1) {
-    return (uint32_t)(((uint64_t)bounds[p + 1] - bounds[p] + (1ull << s1) - 1) >> s1);
+// Exchange regions of this run's slabs (gp_plan.hpp).
+inline int exchange_regions(const gp_sim* s) {
+    return exchange_regions(s->cfg.algorithm == GP_PUSHSUM, s->cfg.topology == GP_IMP3D, s->world, s->bounds);
 }
 
 // gp_setup.hip
-void full_region(uint32_t nloc, int NH, int h, uint32_t& t0, uint32_t& t1, uint32_t& s0, uint32_t& s1);
-void xregion(const Slab& sl, int NH, int h, uint32_t& s_lo, uint32_t& s_hi);
 int create_common(const gp_config* cfg, int mode, int world, int rank, const uint8_t* uid, gp_sim** out);
+
+// gp_topology.hip: the Imp3D in-lists and, across ranks, the lists / bitmaps / slots of the random edges
+int build_imp3d(gp_sim* s);
+
+// gp_xlayout.hip: the exchange buffers of the random-edge / full-topology messages
+int setup_exchange(gp_sim* s);
 
 // gp_exchange.hip
 void build_transfers(gp_sim* s);

@@ -5,9 +5,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "gp_block_plan.hpp"
+#pragma GCC visibility push(hidden)  // the plan's inline functions are no part of the library's surface
+#include "gp_plan.hpp"
+#pragma GCC visibility pop
 #include "gp_device.hpp"
 
 namespace gp {
@@ -48,7 +53,6 @@ __device__ __forceinline__ double2 ld_global(const double2* p) {
     return make_double2(t.x, t.y);
 }
 constexpr int FIN_THREADS = 1024;
-constexpr int RREG_MAX = 8;           // round kernel launches per round, at most (DevState::rregions)
 
 // Device-resident control block.  Written by the single-block finalize kernel
 // between bulk rounds; bulk kernels only read it (plus atomics on the
@@ -267,6 +271,7 @@ hipError_t launch_round_tile_region(const DevState& S, uint32_t round, uint32_t 
 
 // Nodes per tile of the tiled round kernels, in both size classes (gp_tile.hpp).
 constexpr int TILE = 1024;
+static_assert(XTILE == TILE, "the lists' tiles (gp_plan.hpp) are the tile kernels' tiles");
 
 // Arguments of the tiled round kernels (gp_ps_tile.hip, gp_gossip_tile.hip): only what they read.
 struct RoundArgs {
@@ -360,8 +365,6 @@ hipError_t launch_col_seed_init(const DevState& S, hipStream_t st);
 uint32_t rbits_words_for(uint32_t lo, uint32_t nloc);
 RoundArgs make_round_args(const DevState& S, uint32_t round);
 hipError_t launch_round_tile(const DevState& S, uint32_t round, int grid, hipStream_t st);
-bool build_walk_list(const DevState& S, int NR, std::vector<uint32_t>& list, uint32_t woff[][9]);
-bool region_tiles(uint32_t lo, uint32_t nloc, uint64_t g2, int NR, uint32_t* rb);
 hipError_t launch_rbits_init(const DevState& S, int grid, hipStream_t st);
 uint32_t ind4_bytes_for(uint32_t lo, uint32_t nloc);
 hipError_t launch_pack_ind4(const DevState& S, uint32_t wide_at, int grid, hipStream_t st);

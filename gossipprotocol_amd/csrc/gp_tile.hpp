@@ -101,7 +101,7 @@ __device__ __forceinline__ T ld_agent(const T* p) {
 //     consecutive k (y+-1 rows), so lattice gathers and the x+-1 byte planes hit
 //     the XCD's L2 instead of HBM.
 //   walk 3 (k_ps_tile): walk 2's items without the empty ones, listed per XCD
-//     at create time (DevState::wtiles, build_walk_list for gp_setup.hip) and
+//     at create time (DevState::wtiles, build_walk_list, gp_plan.hpp) and
 //     claimed in order from a per-XCD counter (one returning atomic per tile,
 //     issued a tile ahead) on a grid of exactly the resident blocks.  The tiles
 //     an XCD has in flight are then always ~160 consecutive items (20 in-plane

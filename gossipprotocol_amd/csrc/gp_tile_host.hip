@@ -1,9 +1,9 @@
 // gp_tile_host.hip -- the host side of the tiled round kernels, independent of their size
-// class: the kernels' arguments, the slab's tile and region arithmetic, walk 3's tile list,
-// the three set-up kernels that prepare what the tile kernels read, and the entry point
-// that picks the kernel of a round (gp_ps_tile.hip, gp_ps_tile_wide.hip, gp_gossip_tile.hip).
+// class: the kernels' arguments, the three set-up kernels that prepare what the tile kernels
+// read, and the entry point that picks the kernel of a round (gp_ps_tile.hip,
+// gp_ps_tile_wide.hip, gp_gossip_tile.hip).  The slab's tile and region arithmetic and walk 3's
+// tile list: gp_plan.hpp.
 #include <algorithm>
-#include <vector>
 
 #include "gp_internal.hpp"
 
@@ -25,10 +25,6 @@ __global__ __launch_bounds__(SETUP_TPB) void k_rbits_init(const uint8_t* nb, uin
     }
 }
 
-// Tiles covering the ids [lo, lo + nloc) (tiles sit on global multiples of TILE).
-static uint32_t tiles_for(uint32_t lo, uint32_t nloc) {
-    return (uint32_t)(((uint64_t)lo + nloc + TILE - 1) / TILE - lo / TILE);
-}
 // 64-bit words the ballot stores of one round touch (whole tiles) plus slack.
 uint32_t rbits_words_for(uint32_t lo, uint32_t nloc) { return tiles_for(lo, nloc) * (TILE / 64) + 16u; }
 
@@ -75,67 +71,6 @@ RoundArgs make_round_args(const DevState& S, uint32_t round) {
     a.tq = S.tq + (round & 1) * 8 * TQ_STRIDE;
     a.tq_next = S.tq + ((round + 1) & 1) * 8 * TQ_STRIDE;
     return a;
-}
-
-// First plane (relative to the slab's) of region h of NR equal regions over nx planes.  (A last
-// region half the size of the others measured within noise, profiles/r05/rejected/rlast.txt.)
-uint32_t region_plane(uint32_t nx, int NR, int h) {
-    if (h >= NR) return nx;
-    return (uint32_t)((uint64_t)nx * h / NR);
-}
-
-// Region h of NR of a plane-aligned slab: planes [x0 + region_plane(h), x0 + region_plane(h + 1)),
-// whose tiles (relative to lo / TILE) are [rb[h], rb[h + 1]) -- a tile belongs to the plane it
-// starts in (the slab's first tile to the first plane).  False if the slab is not plane-aligned.
-bool region_tiles(uint32_t lo, uint32_t nloc, uint64_t g2, int NR, uint32_t* rb) {
-    if (!g2 || nloc % g2 || lo % g2 || NR < 1) return false;
-    const uint32_t tb = lo / TILE;
-    const uint32_t tend = (uint32_t)(((uint64_t)lo + nloc + TILE - 1) / TILE);
-    const uint32_t x0 = (uint32_t)(lo / g2), nx = (uint32_t)(nloc / g2);
-    for (int h = 0; h <= NR; ++h) {
-        const uint64_t x = x0 + region_plane(nx, NR, h);
-        rb[h] = (x <= x0 ? tb : (uint32_t)std::min<uint64_t>((x * g2 + TILE - 1) / TILE, tend)) - tb;
-    }
-    return true;
-}
-
-// Walk 3's visiting order (host, at create): walk 2's items (TileWalk, gp_tile.hpp) for each
-// of the 8 XCDs, empty items dropped -- every tile of the slab exactly once.
-// list: tiles relative to lo / TILE; woff[0][c]..woff[0][c + 1]: XCD c's items.
-// NR > 1 (launch_round_regions): the planes of region h (region_tiles) dealt to the
-// 8 XCDs in the same way, XCD c's items at woff[h][c]..woff[h][c + 1].
-bool build_walk_list(const DevState& S, int NR, std::vector<uint32_t>& list, uint32_t woff[][9]) {
-    const uint64_t g2 = S.G.g2;
-    if (!g2 || S.nloc % g2 || S.lo % g2 || NR < 1 || NR > RREG_MAX) return false;
-    const uint32_t tb = S.lo / TILE;
-    const uint32_t tend = (uint32_t)(((uint64_t)S.lo + S.nloc + TILE - 1) / TILE);
-    const uint32_t x0 = (uint32_t)(S.lo / g2), nx = (uint32_t)(S.nloc / g2);
-    const uint32_t kp = (uint32_t)((g2 + TILE - 1) / TILE + 1);
-    auto first = [&](uint32_t x) -> uint32_t {
-        return x <= x0 ? tb : (uint32_t)std::min<uint64_t>((x * g2 + TILE - 1) / TILE, tend);
-    };
-    list.clear();
-    for (int h = 0; h < NR; ++h) {
-        const uint32_t r0 = x0 + region_plane(nx, NR, h);
-        const uint32_t nr = x0 + region_plane(nx, NR, h + 1) - r0;
-        for (uint32_t c = 0; c < 8; ++c) {
-            woff[h][c] = (uint32_t)list.size();
-            const uint32_t xa = r0 + (uint32_t)((uint64_t)nr * c / 8);
-            const uint32_t nxa = r0 + (uint32_t)((uint64_t)nr * (c + 1) / 8) - xa;
-            uint32_t nwin = S.tile_wx ? (nxa + S.tile_wx - 1) / S.tile_wx : 1u;
-            if (nwin == 0) nwin = 1;
-            for (uint32_t v = 0; v < nwin && nxa; ++v) {
-                const uint32_t xs = (uint32_t)((uint64_t)nxa * v / nwin), xe = (uint32_t)((uint64_t)nxa * (v + 1) / nwin);
-                for (uint32_t k = 0; k < kp; ++k)
-                    for (uint32_t x = xa + xs; x < xa + xe; ++x) {
-                        const uint32_t ti = first(x) + k;
-                        if (ti < first(x + 1)) list.push_back(ti - tb);
-                    }
-            }
-        }
-        woff[h][8] = (uint32_t)list.size();
-    }
-    return list.size() == (size_t)(tend - tb);
 }
 
 // The tile kernel of round `round`: push-sum in the slab's size class (DevState::tile_wide,

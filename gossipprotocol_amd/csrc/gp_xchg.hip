@@ -662,12 +662,12 @@ hipError_t launch_apply_bits(const uint32_t* bits, uint32_t nwords, const uint32
     return hipGetLastError();
 }
 hipError_t launch_list_count(const ListCountArgs& a, hipStream_t st) {
-    const uint32_t nt = (uint32_t)(((uint64_t)a.lo + a.nloc + XTILE - 1) / XTILE - a.lo / XTILE);
+    const uint32_t nt = tiles_for(a.lo, a.nloc);
     if (nt) hipLaunchKernelGGL(k_list_count, dim3(nt), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 hipError_t launch_list_key(const ListKeyArgs& a, hipStream_t st) {
-    const uint32_t nt = (uint32_t)(((uint64_t)a.lo + a.nloc + XTILE - 1) / XTILE - a.lo / XTILE);
+    const uint32_t nt = tiles_for(a.lo, a.nloc);
     if (nt) hipLaunchKernelGGL(k_list_key, dim3(nt), dim3(256), 0, st, a);
     return hipGetLastError();
 }
@@ -683,30 +683,6 @@ hipError_t launch_halo_pack(const HaloArgs& a, hipStream_t st) {
 hipError_t launch_halo_expand(const HaloArgs& a, hipStream_t st) {
     if (a.n) hipLaunchKernelGGL(k_halo<false>, dim3((a.n + HALO_CHUNK - 1) / HALO_CHUNK), dim3(256), 0, st, a);
     return hipGetLastError();
-}
-
-// Slots per 1024-node chunk of a slab-boundary plane (HaloArgs): the senders toward one x
-// neighbour in a chunk are a sum of Bernoulli(1 / deg) over its nodes (Program.fs:246-260: a
-// boundary plane's nodes have both x neighbours, y / z ones unless on the lattice's edge, and
-// Imp3D's random edge); the largest mean + 12 sigma over the plane's chunks, rounded up to 8.
-// g = 1000: 3D 360 (the chunk of row y = 0), Imp3D 320.
-uint32_t halo_chunk_cap(uint32_t g, bool imp3d) {
-    const uint64_t n = (uint64_t)g * g;
-    double best = 0.0, mu = 0.0, var = 0.0;
-    for (uint64_t i = 0; i <= n; ++i) {
-        if (i == n || (i % HALO_CHUNK == 0 && i > 0)) {
-            best = std::max(best, mu + 12.0 * std::sqrt(var));
-            mu = var = 0.0;
-            if (i == n) break;
-        }
-        const uint32_t y = (uint32_t)(i / g), z = (uint32_t)(i % g);
-        const uint32_t deg = 2u + (y > 0) + (y + 1 < g) + (z > 0) + (z + 1 < g) + (imp3d ? 1u : 0u);
-        const double p = 1.0 / deg;
-        mu += p;
-        var += p * (1.0 - p);
-    }
-    const uint32_t c = (uint32_t)std::ceil(best);
-    return std::min<uint32_t>(HALO_CHUNK, std::max<uint32_t>(8u, (c + 7u) & ~7u));
 }
 hipError_t launch_gather_keys(const uint32_t* key, const uint32_t* src, uint32_t n, uint32_t* out, int grid,
                               hipStream_t st) {

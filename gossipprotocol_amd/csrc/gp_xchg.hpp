@@ -1,12 +1,11 @@
 // gp_xchg.hpp -- argument blocks of the multi-rank kernels (gp_xchg.hip).
-// Not part of the C-ABI.
+// Not part of the C-ABI.  The constants they are sized by (XMAXW, XMAXH, XTILE, HALO_CHUNK) and
+// the buffers' capacities and shapes: gp_plan.hpp.
 #pragma once
 
 #include "gp_internal.hpp"
 
 namespace gp {
-
-constexpr int XMAXW = 16;  // ranks supported by the exchange (one node: 8 GPUs)
 
 // One rank pair's exchange buffer: [count u32 | pad][slots: cap u32][vals: cap (s, w)].
 struct XPeer {
@@ -86,8 +85,6 @@ struct ExpectArgs {
 // the index of the first such message in the destination's vals region -- and the
 // used entries' (s, w) compacted in list order.  The receiver finds a used remote
 // in-edge's message at base + popcount(mask below its bit): no scatter, no slots.
-constexpr uint32_t XTILE = 1024;
-constexpr int XMAXH = 8;           // exchange regions of a slab (push-sum), at most
 constexpr uint32_t XNONE = 0xFFu;  // "no list entry" (local target or no sender)
 
 struct ListPeer {              // send side: region h, destination d
@@ -174,7 +171,6 @@ struct BitsEndsArgs {         // this rank's encodings
 // degree d sends toward the neighbour with probability 1/d, so a chunk made of a plane's
 // boundary row y = 0 (3D: degree 5; Imp3D: 6) expects 205 / 171 senders where an interior
 // chunk expects 146 (Imp3D) -- 12 sigma over the worst, as the other exchange buffers.
-constexpr uint32_t HALO_CHUNK = 1024;
 struct HaloArgs {
     const uint8_t* nb;      // direction bytes of the plane's nodes
     double2* sw;            // the plane's (s, w): read by the pack, written by the expand
@@ -184,8 +180,6 @@ struct HaloArgs {
     uint32_t dir;           // the direction whose senders' (s, w) travel
     unsigned int* overflow;
 };
-inline size_t halo_buf_slots(uint32_t n, uint32_t cap) { return (size_t)((n + HALO_CHUNK - 1) / HALO_CHUNK) * cap; }
-uint32_t halo_chunk_cap(uint32_t g, bool imp3d);
 hipError_t launch_halo_pack(const HaloArgs& a, hipStream_t st);
 hipError_t launch_halo_expand(const HaloArgs& a, hipStream_t st);
 

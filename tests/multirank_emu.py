@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY (tests/test_multirank_gloo.py).  Each torch.distributed
 (gloo) rank owns the slab of node ids the library would give it
-(gp_setup.hip make_bounds: whole x-planes for 3D / Imp3D, contiguous ids for
+(gp_plan.hpp slab_bounds: whole x-planes for 3D / Imp3D, contiguous ids for
 line) and runs SRS v1 rounds for its slab with numpy, talking to the other
 ranks only through the library's exchange plan:
 
@@ -31,7 +31,9 @@ ranks only through the library's exchange plan:
 
 It never calls the HIP library: it checks the decomposition itself (slab
 plan, slot arithmetic, fold order with remote messages, replicated injector)
-against the single-process CPU oracle.  Vectorised Philox4x32-10 follows
+against the single-process CPU oracle.  The plan functions below restate
+gossipprotocol_amd/csrc/gp_plan.hpp, one definition each; tests/test_plan.py
+compares every one of them with the header, compiled for the host.  Vectorised Philox4x32-10 follows
 oracle/srs_py.py (itself pinned by the Random123 known-answer vectors).
 """
 from __future__ import annotations
@@ -127,7 +129,7 @@ class Geometry:
 
 
 def slab_bounds(P, g, topo, W):
-    """gp_setup.hip make_bounds."""
+    """gp_plan.hpp slab_bounds."""
     if topo == "line":
         return [P * w // W for w in range(W + 1)], 1
     if topo == "full":
@@ -136,11 +138,38 @@ def slab_bounds(P, g, topo, W):
 
 
 XTILE = 1024  # the lists' tiles: 1024 ids on global multiples (the push-sum tile kernel's TILE)
+XREGIONS, FB_REGIONS, RREG_MIN_NODES = 4, 2, 1 << 24  # gp_plan.hpp
+
+
+def msg_capacity(m, limit=np.inf):
+    """gp_plan.hpp msg_capacity, the one capacity rule of the exchange buffers: the expected
+    messages per round m + 12 sigma + 64, at most `limit`.  Scalars or arrays."""
+    return np.minimum(np.ceil(m + 12.0 * np.sqrt(m) + 64.0), limit).astype(np.int64)
+
+
+def tiles_for(lo, nloc):
+    """gp_plan.hpp tiles_for: tiles covering the ids [lo, lo + nloc)."""
+    return (lo + nloc + XTILE - 1) // XTILE - lo // XTILE
+
+
+def exchange_regions(push, topo, W, bounds):
+    """gp_plan.hpp exchange_regions: regions of a slab's senders."""
+    if not push:
+        return 1
+    if topo == "Imp3D" and W == 2 and min(bounds[1] - bounds[0], bounds[2] - bounds[1]) >= RREG_MIN_NODES:
+        return 8
+    return XREGIONS if topo == "Imp3D" else FB_REGIONS
+
+
+def xregion(lo, nloc, tb, NH, h):
+    """gp_plan.hpp xregion with lists: local sender ids [s_lo, s_hi) of the tiles [tb[h], tb[h + 1])."""
+    at = lambda t: min(nloc, max(0, (lo // XTILE + t) * XTILE - lo))
+    return at(tb[h]), nloc if h + 1 == NH else at(tb[h + 1])
 
 
 def region_tiles(lo, nloc, g2, NH, nt):
     """Tile boundaries (relative to lo // XTILE) of the NH exchange regions of a slab
-    (gp_tile_host.hip region_tiles): region h holds the planes [x0 + nx h / NH, x0 + nx (h + 1) / NH),
+    (gp_plan.hpp list_region_tiles): region h holds the planes [x0 + nx h / NH, x0 + nx (h + 1) / NH),
     a tile belonging to the plane it starts in; a slab not made of whole planes is cut
     into equal tile counts."""
     if not g2 or nloc % g2 or lo % g2:
@@ -156,9 +185,9 @@ def region_tiles(lo, nloc, g2, NH, nt):
 
 class ListPlan:
     """Imp3D push-sum over several ranks: the sender-ordered lists (gp_xchg.hpp,
-    gp_setup.hip build_lists / setup_exchange).  List L_ab = slab a's senders whose
+    gp_topology.hip build_lists / gp_xlayout.hip setup_exchange; the tables: gp_plan.hpp).  List L_ab = slab a's senders whose
     random edge lands on slab b, in id order, cut into the slab's tiles and NH
-    regions of consecutive tiles (region_tiles: whole planes, gp_setup.hip XREGIONS = 4);
+    regions of consecutive tiles (region_tiles: whole planes, gp_plan.hpp XREGIONS = 4);
     every (tile, b) segment starts on a 64-entry
     boundary.  Computed from the global random edges, like every rank of the
     library does for every slab."""
@@ -176,7 +205,7 @@ class ListPlan:
         for a in range(W):
             lo, hi = bounds[a], bounds[a + 1]
             t_of = ids[lo:hi] // XTILE - lo // XTILE            # tile of each sender (relative)
-            nt = (hi + XTILE - 1) // XTILE - lo // XTILE
+            nt = tiles_for(lo, hi - lo)
             tb = np.array(region_tiles(lo, hi - lo, g * g, NH, nt))
             region_of_tile = np.searchsorted(tb[1:NH], np.arange(nt), side="right")
             h_of = region_of_tile[t_of]
@@ -201,7 +230,7 @@ class ListPlan:
         for a in range(W):
             lo, hi = bounds[a], bounds[a + 1]
             np.add.at(n_edges, (self.region[lo:hi], a, owner[lo:hi]), 1)
-        self.cap = np.minimum(np.ceil(mu + 12.0 * np.sqrt(mu) + 64.0), n_edges).astype(np.int64)
+        self.cap = msg_capacity(mu, n_edges)
         for a in range(W):
             self.cap[:, a, a] = 0
         self.owner, self.slab = owner, slab
@@ -237,18 +266,17 @@ class ListPlan:
 
 
 def full_capacity(na, nb, P):
-    """Per-pair message capacity of the full-topology exchange (gp_setup.hip
-    setup_exchange): messages a -> b are at most Binomial(na, nb / (P - 1))."""
-    m = na * nb / (P - 1)
-    return int(min(np.ceil(m + 12.0 * np.sqrt(m) + 64.0), na))
+    """Per-pair message capacity of the full-topology gossip exchange (gp_plan.hpp
+    full_pair_cap): messages a -> b are at most Binomial(na, nb / (P - 1))."""
+    return int(msg_capacity(float(na) * float(nb) / float(P - 1), na))
 
 
-FB_TB = 12       # gp_fullbin.hpp: fine tiles of 4096 receivers
-FBM_KEYS = 192   # gp_fullbin.hip: keys of all ranks' coarse bins together, at most
+FB_TB = 12       # gp_plan.hpp: fine tiles of 4096 receivers
+FBM_KEYS = 192   # gp_plan.hpp: keys of all ranks' coarse bins together, at most
 
 
 def full_bin_plan(nrecv, fused=False):
-    """gp_fullbin.hip full_bin_plan: coarse bins of 2^s1 receivers, fine tiles of 4096; the
+    """gp_plan.hpp full_bin_plan: coarse bins of 2^s1 receivers, fine tiles of 4096; the
     fused fold (one rank) takes coarse bins one size smaller, at most 1024 of them."""
     fb_tb, cap2 = 12, 4992
     bits = 1
@@ -268,7 +296,7 @@ def full_bin_plan(nrecv, fused=False):
 
 
 def full_bin_multi_s1(bounds):
-    """Coarse-bin size 2^s1 every rank uses on the full topology (gp_fullbin.hip
+    """Coarse-bin size 2^s1 every rank uses on the full topology (gp_plan.hpp
     full_bin_multi_s1): the smallest >= a fine tile that keeps all ranks' bins together at
     most FBM_KEYS."""
     s1 = FB_TB
@@ -281,17 +309,48 @@ def full_bin_multi_s1(bounds):
 
 def full_bin_multi_cap(n, s1, P):
     """Messages a region of n senders sends to one coarse bin (2^s1 receivers) of any rank,
-    at most (gp_fullbin.hip full_bin_multi_cap): Binomial(n, 2^s1 / (P - 1)) + 12 sigma + 64."""
-    m = n * (1 << s1) / max(P - 1, 1)
-    return int(min(np.ceil(m + 12.0 * np.sqrt(m) + 64.0), n))
+    at most (gp_plan.hpp full_bin_multi_cap): Binomial(n, 2^s1 / (P - 1)) + 12 sigma + 64."""
+    return int(msg_capacity(float(n) * float(1 << s1) / float(max(P - 1, 1)), n))
+
+
+def fb_bins_bytes(nb, cap):
+    """gp_plan.hpp fb_bins_bytes: [counts | sender ids | payloads], 16-B aligned parts; nothing
+    for no bins or no capacity."""
+    if not nb or not cap:
+        return 0
+    return (nb * 4 + 15) // 16 * 16 + (nb * cap * 4 + 15) // 16 * 16 + nb * cap * 16
 
 
 def full_region(n, NH, h):
-    """Region h of NH of a slab of n ids (gp_setup.hip full_region): fine tiles [t0, t1),
+    """Region h of NH of a slab of n ids (gp_plan.hpp full_region): fine tiles [t0, t1),
     local sender ids [s0, s1)."""
     nt = -(-n // (1 << FB_TB))
     t0, t1 = nt * h // NH, nt * (h + 1) // NH
     return min(n, t0 << FB_TB), min(n, t1 << FB_TB)
+
+
+HALO_CHUNK = 1024  # gp_plan.hpp: nodes per chunk of a compacted halo plane
+
+
+def halo_send_prob(g, imp3d):
+    """Per node of a slab-boundary plane (id y g + z), the probability 1 / deg that it sends toward
+    one x neighbour."""
+    y, z = np.divmod(np.arange(g * g), g)
+    deg = 2 + (y > 0) + (y < g - 1) + (z > 0) + (z < g - 1) + (1 if imp3d else 0)
+    return 1.0 / deg
+
+
+def halo_chunk_cap(g, imp3d):
+    """gp_plan.hpp halo_chunk_cap: the senders toward one x neighbour in a 1024-node chunk of a
+    slab-boundary plane are a sum of Bernoulli(1 / deg); the largest mean + 12 sigma over the
+    plane's chunks, rounded up to 8.  The header adds each chunk up node by node; so does
+    np.cumsum (np.sum adds pairwise, which can round differently)."""
+    p = halo_send_prob(g, imp3d)
+    best = 0.0
+    for c0 in range(0, g * g, HALO_CHUNK):
+        q = p[c0:c0 + HALO_CHUNK]
+        best = max(best, float(np.cumsum(q)[-1]) + 12.0 * math.sqrt(float(np.cumsum(q * (1.0 - q))[-1])))
+    return min(HALO_CHUNK, max(8, (math.ceil(best) + 7) // 8 * 8))
 
 
 def full_target(i, k):

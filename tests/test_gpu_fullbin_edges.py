@@ -1,7 +1,7 @@
 """GPU: full-topology push-sum (gp_fullbin.hip: k_fb_send, k_fbm_send, k_fb_split, k_fb_fold) at its
 slab, bin-size and capacity edges, bit-exact against the CPU oracle on s, w, flags and per-round
 alerts.  Every case first shows on the CPU -- from the slab bounds (multirank_emu.slab_bounds /
-full_region / full_bin_multi_s1 / full_bin_plan, restatements of the library's host code) and from the
+full_region / full_bin_multi_s1 / full_bin_plan, restatements of gp_plan.hpp that test_plan.py compares with it) and from the
 Philox draws of the oracle's own senders (multirank_emu.uniform / full_target; the senders of round r
 are the nodes whose active flag the oracle shows at its start) -- that it is where it claims to be.
 

@@ -52,7 +52,7 @@ def test_virtual_ranks_parity(kernel, n, topo, alg, seed, rounds, chk, ranks, mo
     """default: the product library's own kernel choice; the others force a
     variant through the experiments build (GP_KERNEL).  regions: Imp3D push-sum
     with the round kernel run region by region (GP_RREGIONS=1; the product does
-    so for slabs of >= 2^24 nodes, gp_setup.hip round_regions) -- four launches per
+    so for slabs of >= 2^24 nodes, gp_setup.hip round_regions, gp_plan.hpp round_regions_on) -- four launches per
     round, the lists of each region sent behind the next, the receive buffer by
     round parity, regions holding no plane at 8 000 nodes / 16 ranks."""
     if kernel == "col" and (topo == "line" or alg == "push-sum"):

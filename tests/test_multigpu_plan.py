@@ -1,7 +1,8 @@
 """CPU: the one-node 8-GPU plan of BASELINE's multi-GPU configurations, computed on
-the host (no GPU, no RCCL).  The library's slab plan (gp_setup.hip make_bounds)
-and exchange capacities (gp_setup.hip setup_exchange: expected messages per rank
-pair + 12 sigma + 64) are restated here; the tests check that
+the host (no GPU, no RCCL).  The library's slab plan (gp_plan.hpp slab_bounds)
+and exchange capacities (gp_plan.hpp msg_capacity: expected messages per rank
+pair + 12 sigma + 64) come from their restatements in tests/multirank_emu.py, which
+tests/test_plan.py compares with the header; the tests check that
 
   * C5 (Imp3D push-sum, n = 1e9) and C4 (full push-sum, n = 1e8) fit one
     MI355X's 288 GB per rank at world 8, setup temporaries included;
@@ -17,8 +18,9 @@ import pytest
 
 import numpy as np
 
-from tests.multirank_emu import (DIR_RANDOM, Geometry, S_PUSHSUM, S_TOPO, full_bin_multi_cap, full_bin_multi_s1,
-                                 full_bin_plan, full_region, resolve, slab_bounds, uniform)
+from tests.multirank_emu import (DIR_RANDOM, Geometry, S_PUSHSUM, S_TOPO, fb_bins_bytes, full_bin_multi_cap,
+                                 full_bin_multi_s1, full_bin_plan, full_region, halo_chunk_cap, halo_send_prob,
+                                 msg_capacity as cap_of, resolve, slab_bounds, uniform)
 
 HBM_BYTES = 288e9
 GAUSS_12SIGMA_TAIL = 1.8e-33  # P(Z > 12)
@@ -56,10 +58,6 @@ def imp3d_pair_stats(P, g, W):
             mu[a, b] = s * frac
             var[a, b] = mu[a, b] * (1 - 1 / 7)
     return bounds, mu, var
-
-
-def cap_of(mu):
-    return math.ceil(mu + 12.0 * math.sqrt(mu) + 64.0)
 
 
 def imp3d_rank_bytes(nloc, halo, nedges, W, caps_out, caps_in, P):
@@ -103,11 +101,6 @@ def test_c5_imp3d_pushsum_1e9_world8_plan():
         assert steady < 0.1 * HBM_BYTES
     # a convergence run of 10^5 rounds x 56 pairs stays far from an overflow
     assert 1e5 * W * (W - 1) * GAUSS_12SIGMA_TAIL < 1e-25
-
-
-def fb_bins_bytes(nb, cap):
-    """gp_fullbin.hip fb_bins_bytes: [counts | sender ids | payloads], 16-B aligned parts."""
-    return (nb * 4 + 15) // 16 * 16 + (nb * cap * 4 + 15) // 16 * 16 + nb * cap * 16
 
 
 @pytest.mark.parametrize("W", [2, 4, 8])
@@ -174,7 +167,7 @@ def test_realised_imp3d_counts_stay_below_capacity_world8():
         half += (t_rel >= nt * h // NH).astype(np.int64)
     mu = np.zeros((NH, W, W))
     np.add.at(mu, (half, src_rank, dst_rank), inv_deg)
-    cap = np.vectorize(lambda m: min(cap_of(m), 10**9))(mu)
+    cap = cap_of(mu, 10**9)
     worst = 0.0
     off = np.broadcast_to(~np.eye(W, dtype=bool), (NH, W, W))
     for r in range(40):
@@ -202,20 +195,6 @@ def test_fused_full_bin_plan_fits(P):
         assert (nb1, nb1_rule) == (191, 96)
 
 
-def halo_chunk_cap(g, imp3d):
-    """gp_xchg.hip halo_chunk_cap: the senders toward one x neighbour in a 1024-node chunk of a
-    slab-boundary plane are a sum of Bernoulli(1 / deg); the largest mean + 12 sigma over the
-    plane's chunks, rounded up to 8."""
-    y, z = np.divmod(np.arange(g * g), g)
-    deg = 2 + (y > 0) + (y < g - 1) + (z > 0) + (z < g - 1) + (1 if imp3d else 0)
-    p = 1.0 / deg
-    best = 0.0
-    for c0 in range(0, g * g, 1024):
-        q = p[c0:c0 + 1024]
-        best = max(best, q.sum() + 12.0 * math.sqrt((q * (1 - q)).sum()))
-    return min(1024, max(8, (math.ceil(best) + 7) // 8 * 8)), p
-
-
 def poisson_binomial_tail(q, k):
     """P(sum of Bernoulli(q_i) > k), exactly (dynamic programme over the chunk's nodes)."""
     dist = np.zeros(len(q) + 2)
@@ -233,7 +212,7 @@ def test_halo_chunk_capacity_covers_boundary_rows(g, imp3d):
     with probability ~3e-5 per chunk and round on 3D at g = 1000 (a loud but spurious GP_ESTATE).
     The capacity rule keeps every chunk's exact overflow probability negligible over a
     convergence run (every round, both directions, every slab boundary)."""
-    cap, p = halo_chunk_cap(g, imp3d)
+    cap, p = halo_chunk_cap(g, imp3d), halo_send_prob(g, imp3d)
     worst = max(poisson_binomial_tail(p[c0:c0 + 1024], cap) for c0 in (0, 1024, (g * g // 1024) * 1024 - 1024))
     assert worst < 1e-25
     if g == 1000:
