@@ -197,9 +197,14 @@ struct Scratch {
 // senders (rq) and cross ranks as counts; no bitmap, in-edge tags or slots.
 inline bool col_gossip_counts(const DevState& S) { return S.topo == IMP3D && S.alg == GOSSIP && S.kernel == KERNEL_COL; }
 
-// Exchange regions of this run's slabs (gp_plan.hpp).
+// Exchange regions of this run's slabs (gp_plan.hpp).  GP_XREGIONS=8 (experiments): the eight
+// regions of two ranks with large slabs at any slab size and world, Imp3D push-sum only; any
+// other value is ignored.
 inline int exchange_regions(const gp_sim* s) {
-    return exchange_regions(s->cfg.algorithm == GP_PUSHSUM, s->cfg.topology == GP_IMP3D, s->world, s->bounds);
+    const bool push = s->cfg.algorithm == GP_PUSHSUM, imp3d = s->cfg.topology == GP_IMP3D;
+    if (const char* e = exp_env("GP_XREGIONS"))
+        if (push && imp3d && s->world > 1 && std::atoi(e) == 8) return 8;
+    return exchange_regions(push, imp3d, s->world, s->bounds);
 }
 
 // gp_setup.hip

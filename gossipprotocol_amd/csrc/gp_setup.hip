@@ -154,6 +154,9 @@ int setup_halo(gp_sim* s) {
     const bool lattice = s->cfg.topology == GP_3D || s->cfg.topology == GP_IMP3D;
     if (!lattice || s->cfg.algorithm != GP_PUSHSUM || s->world < 2 || s->halo < HALO_CHUNK) return GP_OK;
     s->halo_cap = halo_chunk_cap((uint32_t)s->g, s->cfg.topology == GP_IMP3D);
+    // (GP_HALO_CAP, experiments: fewer slots per chunk, to put a round's fullest chunk at the last
+    // slot or one past it -- never more than the plan's)
+    if (const char* e = exp_env("GP_HALO_CAP")) s->halo_cap = std::min<uint32_t>(s->halo_cap, (uint32_t)std::max(1, std::atoi(e)));
     s->halo_slots = halo_buf_slots(s->halo, s->halo_cap);
     int rc;
     for (Slab& sl : s->slab) {

@@ -75,6 +75,9 @@ CASES = [
     (4, 40000, "full", "push-sum", 9, 30),
     (2, 200**3, "Imp3D", "gossip", 4, 150),  # g = 200: the column kernel, random-edge counts through the exchange
     (3, 200**3, "Imp3D", "gossip", 6, 120),
+    # g = 33: planes of 1089 = 1024 + 65 ids -- list tiles shared by two slabs and a halo plane of two
+    # chunks, the second of 65 nodes (tests/test_gpu_list_edges.py), over the RCCL transfers; a middle rank
+    (3, 33**3, "Imp3D", "push-sum", 1, 60),
 ]
 
 

@@ -115,8 +115,13 @@ def imp3d_slabs(g, W):
 
 
 # g = 40 / W = 8 (the emulation's plan); g = 20: slabs plane-aligned but tile-unaligned; a line slab
-# (no planes: equal tile counts); g = 1000: the large configuration and the eight-region rule
-@pytest.mark.parametrize("g,W", [(40, 8), (20, 2), (20, 3), (0, 3), (1000, 2), (1000, 8)])
+# (no planes: equal tile counts); g = 1000: the large configuration and the eight-region rule; then the
+# shapes of tests/test_gpu_list_edges.py (groups A-E; NH = 8 at W = 2 is its group C)
+LIST_EDGE_SHAPES = [(32, 2), (64, 4), (64, 2), (64, 8), (64, 16), (48, 2), (48, 3), (33, 2), (33, 3), (5, 5), (3, 3),
+                    (2, 2), (19, 16), (20, 16), (6, 2), (31, 2), (31, 3), (32, 3)]
+
+
+@pytest.mark.parametrize("g,W", [(40, 8), (20, 2), (20, 3), (0, 3), (1000, 2), (1000, 8)] + LIST_EDGE_SHAPES)
 @pytest.mark.parametrize("NH", [4, 8])
 def test_tiles_and_regions(plan, g, W, NH):
     bounds = imp3d_slabs(g, W) if g else emu.slab_bounds(100001, 0, "line", W)[0]
@@ -157,26 +162,44 @@ def test_exchange_regions_and_the_eight_region_rule(plan):
     assert got == [[1, 1], [1, 1], [0, 1], [1, 1], [0, 1], [1, 0], [1, 0]]
 
 
-@pytest.mark.parametrize("g", [100, 465, 1000, 1625])
+@pytest.mark.parametrize("g", [100, 465, 1000, 1625, 31, 32, 33, 2, 3, 5, 6, 19, 48, 64])
 def test_halo_chunk_cap(plan, g):
     got = plan([("halo_cap", g, 0), ("halo_cap", g, 1)])
     caps = [emu.halo_chunk_cap(g, False), emu.halo_chunk_cap(g, True)]
     assert got == [[caps[0]], [caps[1]]]
     assert plan([("halo_slots", g * g, caps[0])]) == [[-(-g * g // 1024) * caps[0]]]
+    assert plan([("halo_slots", g * g, caps[1])]) == [[-(-g * g // 1024) * caps[1]]]
+
+
+def make_list_plan(g, W, seed, NH=4):
+    P = g ** 3
+    bounds, _ = emu.slab_bounds(P, g, "Imp3D", W)
+    rnd = emu.uniform(seed, emu.S_TOPO, np.arange(P), 0, P - 1)
+    return emu.ListPlan(P, g, W, bounds, rnd, emu.Geometry(P, g, "Imp3D", seed), NH=NH), rnd, g
 
 
 @pytest.fixture(scope="module")
 def list_plan():
     """The plan test_multigpu_plan.py draws: P = 64000 (g = 40), W = 8, seed 5."""
-    n, W, seed = 64000, 8, 5
-    P, _, g = emu.resolve(n, "Imp3D")
-    bounds, _ = emu.slab_bounds(P, g, "Imp3D", W)
-    rnd = emu.uniform(seed, emu.S_TOPO, np.arange(P), 0, P - 1)
-    return emu.ListPlan(P, g, W, bounds, rnd, emu.Geometry(P, g, "Imp3D", seed)), rnd, g
+    return make_list_plan(40, 8, 5)
+
+
+# the plans of tests/test_gpu_list_edges.py, its seeds: (g, W, seed, NH)
+LIST_EDGE_PLANS = [(32, 2, 1, 4), (64, 4, 1, 4), (64, 8, 1, 4), (64, 16, 1, 4), (48, 2, 1, 4), (48, 3, 1, 4), (33, 2, 1, 4),
+                   (33, 3, 1, 4), (5, 5, 1, 4), (3, 3, 1, 4), (2, 2, 1, 4), (2, 2, 6, 4), (19, 16, 1, 4), (33, 2, 1, 8),
+                   (64, 2, 1, 8), (6, 2, 1, 8)]
 
 
 def test_list_tables_and_chunk_offsets(plan, list_plan):
-    lp, rnd, g = list_plan
+    check_list_tables_and_chunk_offsets(plan, *list_plan)
+
+
+@pytest.mark.parametrize("case", LIST_EDGE_PLANS, ids=lambda c: "g%d-W%d-s%d-NH%d" % c)
+def test_list_tables_and_chunk_offsets_at_list_edges(plan, case):
+    check_list_tables_and_chunk_offsets(plan, *make_list_plan(*case))
+
+
+def check_list_tables_and_chunk_offsets(plan, lp, rnd, g):
     W, NH, bounds = lp.W, lp.NH, lp.bounds
     q, want = [], []
     for b in range(W):
