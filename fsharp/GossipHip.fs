@@ -94,6 +94,66 @@ extern int gp_ensemble_read_state(nativeint ensemble, int64 ``member``, int64 fi
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern void gp_ensemble_destroy(nativeint ensemble)
 
+// State summary: what a run computed, reduced on the device (INTEGRATION.md §2.3).
+// gp_summary is 304 bytes; the fixed arrays are spelled out field by field to stay blittable.
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type GpSummary =
+    val mutable First: int64
+    val mutable Count: int64
+    val mutable Population: int64
+    val mutable Rounds: int64
+    val mutable Algorithm: int32
+    val mutable Reserved: int32
+    val mutable Active: int64
+    val mutable Converged: int64
+    val mutable CHist0: int64
+    val mutable CHist1: int64
+    val mutable CHist2: int64
+    val mutable CHist3: int64
+    val mutable CHist4: int64
+    val mutable CHist5: int64
+    val mutable CHist6: int64
+    val mutable CHist7: int64
+    val mutable CHist8: int64
+    val mutable CHist9: int64
+    val mutable CHist10: int64
+    val mutable CHist11Plus: int64
+    val mutable CMax: int32
+    val mutable Reserved2: int32
+    val mutable CntHist0: int64
+    val mutable CntHist1: int64
+    val mutable CntHist2: int64
+    val mutable CntHist3: int64
+    val mutable EstMin: double
+    val mutable EstMax: double
+    val mutable WMin: double
+    val mutable WMax: double
+    val mutable ErrMax: double
+    val mutable ErrMaxNode: int64
+    val mutable WithinTol: int64
+    val mutable Tol: double
+    val mutable SumSHi: double
+    val mutable SumSLo: double
+    val mutable SumWHi: double
+    val mutable SumWLo: double
+    val mutable SumSqErrHi: double
+    val mutable SumSqErrLo: double
+
+[<Literal>]
+let GP_SCOPE_LOCAL = 0
+
+[<Literal>]
+let GP_SCOPE_GLOBAL = 1
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gp_summary_take(nativeint sim, double tol, int scope, GpSummary& result)
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gp_summary_merge(GpSummary& a, GpSummary& b, GpSummary& result)
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gp_ensemble_summary(nativeint ensemble, double tol, [<Out>] GpSummary[] summaries)
+
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern nativeint gp_last_error()
 

@@ -21,6 +21,7 @@ GP_GOSSIP, GP_PUSHSUM = 0, 1
 GP_STATUS_CONVERGED, GP_STATUS_MAX_ROUNDS, GP_STATUS_RUNNING = 0, 1, 2
 GP_FLAG_KERNEL_TIMING = 1
 GP_FLAG_VIRTUAL_RANKS = 2
+GP_SCOPE_LOCAL, GP_SCOPE_GLOBAL = 0, 1
 ERRORS = {-1: "GP_EINVAL", -2: "GP_ENOMEM", -3: "GP_EHIP", -4: "GP_ENCCL", -5: "GP_ESTATE", -6: "GP_ENODEV"}
 
 
@@ -48,6 +49,39 @@ class GpMember(C.Structure):
     """One ensemble member (gp_member)."""
     _fields_ = [("seed", C.c_uint64), ("rounds", C.c_int64), ("converged", C.c_int64),
                 ("seed_node", C.c_int64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GpSummary(C.Structure):
+    """What a run computed, reduced on the device (gp_summary)."""
+    _fields_ = [("first", C.c_int64), ("count", C.c_int64), ("population", C.c_int64), ("rounds", C.c_int64),
+                ("algorithm", C.c_int32), ("reserved", C.c_int32), ("active", C.c_int64), ("converged", C.c_int64),
+                ("c_hist", C.c_int64 * 12), ("c_max", C.c_int32), ("reserved2", C.c_int32),
+                ("cnt_hist", C.c_int64 * 4), ("est_min", C.c_double), ("est_max", C.c_double),
+                ("w_min", C.c_double), ("w_max", C.c_double), ("err_max", C.c_double),
+                ("err_max_node", C.c_int64), ("within_tol", C.c_int64), ("tol", C.c_double),
+                ("sum_s", C.c_double * 2), ("sum_w", C.c_double * 2), ("sum_sqerr", C.c_double * 2)]
+
+    # derived from the double-double sums (push-sum; 0 / nan-free for gossip, whose sums are 0)
+    @property
+    def mass(self):
+        """(sum of s, sum of w): what push-sum conserves."""
+        return self.sum_s[0], self.sum_w[0]
+
+    @property
+    def mean_estimate(self):
+        """sum of s over sum of w: the average the covered nodes hold between them."""
+        return self.sum_s[0] / self.sum_w[0] if self.sum_w[0] else 0.0
+
+    @property
+    def rms_error(self):
+        """Root mean square over the covered nodes of e = s / w - (P - 1) / 2."""
+        return (self.sum_sqerr[0] / self.count) ** 0.5 if self.count else 0.0
+
+    def merge(self, other):
+        """This summary joined with the one of the adjacent, higher id range (gp_summary_merge)."""
+        out = GpSummary()
+        check(lib().gp_summary_merge(C.byref(self), C.byref(other), C.byref(out)))
+        return out
 
 
 # (name, restype, argtypes) for every symbol include/gossip_hip.h declares
@@ -78,6 +112,9 @@ SIGNATURES = [
     ("gp_ensemble_members", _i32, [_vp, C.POINTER(GpMember)]),
     ("gp_ensemble_read_state", _i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("gp_ensemble_destroy", None, [_vp]),
+    ("gp_summary_take", _i32, [_vp, C.c_double, _i32, C.POINTER(GpSummary)]),
+    ("gp_summary_merge", _i32, [C.POINTER(GpSummary), C.POINTER(GpSummary), C.POINTER(GpSummary)]),
+    ("gp_ensemble_summary", _i32, [_vp, C.c_double, C.POINTER(GpSummary)]),
 ]
 
 _libs = {}

@@ -1,7 +1,7 @@
 // gossip_cli.cpp -- command-line front-end with the reference's surface:
 //
 //   gossip <num_nodes> <topology> <algorithm> [--seed S] [--max-rounds R]
-//          [--gpus G] [--device D] [--stats]
+//          [--gpus G] [--device D] [--stats] [--summary[=TOL]]
 //
 // mirrors `dotnet run num_nodes topology algorithm` (README.md:1, argv parse
 // Program.fs:32-34) and its stdout contract: "Gossip Starts" / "Push Sum Starts"
@@ -10,6 +10,10 @@
 // "option invalid" (Program.fs:207) and, unlike the reference (which then
 // blocks on ReadKey, Program.fs:282), exits 2; an unknown topology (silently
 // ignored by Program.fs:279) is reported and exits 2.
+//
+// --summary[=TOL] (default 1e-10) adds one line after everything else: what the run computed
+// (gp_summary_take over the whole network, reduced on the device).  Without the
+// flag the output is unchanged.
 //
 // The timed region matches the reference's Stopwatch: it starts after the
 // topology build (Program.fs:194,219,264) and stops at the T-th alert
@@ -26,6 +30,7 @@
 // each with its own RCCL host id (RCCL's socket transport on loopback), for
 // boxes with a single MI355X.
 #include <cerrno>
+#include <cmath>
 #include <csignal>
 #include <cstdio>
 #include <cstdlib>
@@ -45,7 +50,7 @@ namespace {
 int usage() {
     std::fprintf(stderr,
                  "usage: gossip <num_nodes> <line|full|3D|Imp3D> <gossip|push-sum> "
-                 "[--seed S] [--max-rounds R] [--gpus G] [--device D] [--stats]\n");
+                 "[--seed S] [--max-rounds R] [--gpus G] [--device D] [--stats] [--summary[=TOL]]\n");
     return 2;
 }
 
@@ -54,7 +59,27 @@ struct Args {
     int gpus = 1;
     bool device_set = false;  // --device given: with gpus > 1, every rank on that device
     bool stats = false;
+    bool summary = false;     // --summary[=TOL]: one more line, the whole network's gp_summary
+    double tol = 1e-10;
 };
+
+// The --summary line (the same text as python -m gossipprotocol_amd prints).
+void print_summary(const gp_summary& m) {
+    if (m.algorithm == GP_GOSSIP) {
+        std::printf("Summary: rounds=%lld nodes=%lld active=%lld converged=%lld heard=%lld c_max=%d c_hist=",
+                    (long long)m.rounds, (long long)m.count, (long long)m.active, (long long)m.converged,
+                    (long long)(m.count - m.c_hist[0]), m.c_max);
+        for (int k = 0; k < 12; ++k) std::printf("%s%lld", k ? "," : "", (long long)m.c_hist[k]);
+        std::printf("\n");
+    } else {
+        std::printf("Summary: rounds=%lld nodes=%lld active=%lld converged=%lld mean=%.17g est_min=%.17g est_max=%.17g "
+                    "err_max=%.6e node=%lld rms_err=%.6e within_tol=%lld tol=%g sum_s=%.17g sum_w=%.17g\n",
+                    (long long)m.rounds, (long long)m.count, (long long)m.active, (long long)m.converged,
+                    m.sum_w[0] != 0.0 ? m.sum_s[0] / m.sum_w[0] : 0.0, m.est_min, m.est_max, m.err_max,
+                    (long long)m.err_max_node, m.count > 0 ? std::sqrt(m.sum_sqerr[0] / (double)m.count) : 0.0,
+                    (long long)m.within_tol, m.tol, m.sum_s[0], m.sum_w[0]);
+    }
+}
 
 // Run this process's share: the whole network (world 1) or rank `rank` of
 // `world`.  Only rank 0 writes the stdout contract.  Returns the exit code.
@@ -98,6 +123,12 @@ int run(const Args& a, int rank, int world, const char* rdv) {
         gp_destroy(sim);
         return 1;
     }
+    gp_summary sum;
+    if (a.summary && (rc = gp_summary_take(sim, a.tol, GP_SCOPE_GLOBAL, &sum))) {  // every rank: collective
+        std::fprintf(stderr, "[rank %d/%d] gp_summary_take failed (%d): %s\n", rank, world, rc, gp_last_error());
+        gp_destroy(sim);
+        return 1;
+    }
     int code = 0;
     if (res.status != GP_STATUS_CONVERGED) code = 3;
     if (lead) {
@@ -112,6 +143,7 @@ int run(const Args& a, int rank, int world, const char* rdv) {
                         (long long)res.rounds, (long long)res.population, (long long)res.threshold, world,
                         res.node_updates_per_s,  // whole network: P * rounds / elapsed
                         res.elapsed_ms > 0 ? res.hbm_bytes_alg / (res.elapsed_ms * 1e6) : 0.0);
+        if (a.summary) print_summary(sum);
         std::fflush(stdout);
     }
     gp_destroy(sim);
@@ -232,6 +264,16 @@ int main(int argc, char** argv) {
             a.device_set = true;
         } else if (s == "--gpus" && i + 1 < argc) a.gpus = std::atoi(argv[++i]);
         else if (s == "--stats") a.stats = true;
+        else if (s == "--summary") a.summary = true;
+        else if (s.rfind("--summary=", 0) == 0) {
+            char* e2 = nullptr;
+            a.tol = std::strtod(s.c_str() + 10, &e2);
+            if (e2 == s.c_str() + 10 || *e2 || !(a.tol >= 0.0) || !std::isfinite(a.tol)) {
+                std::fprintf(stderr, "--summary=TOL: TOL must be a finite number >= 0: '%s'\n", s.c_str() + 10);
+                return 2;
+            }
+            a.summary = true;
+        }
         else return usage();
     }
     if (a.gpus < 1) {

@@ -5,6 +5,9 @@
 
 #include "gp_host.hpp"
 #include "gp_ensemble.hpp"
+#pragma GCC visibility push(hidden)
+#include "gp_summary_dev.hpp"
+#pragma GCC visibility pop
 
 namespace {
 
@@ -63,6 +66,7 @@ struct gp_ensemble {
     std::vector<void*> allocs;
     std::vector<gp_member> rec;    // host copy of the member records, refreshed after every launch
     std::vector<uint32_t> running; // unfinished members, in member order
+    SumAcc* d_sum = nullptr;       // gp_ensemble_summary: one record per member, allocated at the first call
 };
 
 namespace {
@@ -281,6 +285,41 @@ int gp_ensemble_read_state(gp_ensemble* e, int64_t member, int64_t first, int64_
         HIP_TRY(hipStreamSynchronize(e->stream));
         if (c) std::fill(c, c + n, 0);
     }
+    return GP_OK;
+}
+
+int gp_ensemble_summary(gp_ensemble* e, double tol, gp_summary* out) {
+    if (!e || !out) {
+        set_err("gp_ensemble_summary: null argument");
+        return GP_EINVAL;
+    }
+    if (!(tol >= 0.0) || !std::isfinite(tol)) {
+        set_err("gp_ensemble_summary: tol must be finite and >= 0 (got %g)", tol);
+        return GP_EINVAL;
+    }
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    const size_t n = (size_t)e->nseeds;
+    if (!e->d_sum) {
+        const int rc = ens_alloc(e, &e->d_sum, n);
+        if (rc) return rc;
+    }
+    // the members' stored state (every launch leaves it in HBM), one workgroup per member
+    SumEnsArgs a{};
+    a.c = e->args.c;
+    a.s = e->args.s;
+    a.w = e->args.w;
+    a.fl = e->args.fl;
+    a.rec = e->args.rec;
+    a.P = (uint32_t)e->P;
+    a.mu = (double)(e->P - 1) * 0.5;
+    a.tol = tol;
+    a.out = e->d_sum;
+    const int alg = e->cfg.algorithm == GP_PUSHSUM ? PUSHSUM : GOSSIP;
+    HIP_TRY(summary_ens_launch(alg, a, (uint32_t)n, e->stream));
+    std::vector<SumAcc> h(n);
+    HIP_TRY(hipMemcpyAsync(h.data(), e->d_sum, n * sizeof(SumAcc), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t m = 0; m < n; ++m) summary_from_acc(h[m], alg, 0, e->P, e->P, e->rec[m].rounds, tol, &out[m]);
     return GP_OK;
 }
 

@@ -155,6 +155,9 @@ struct gp_sim {
     hipStream_t xstream = nullptr;
     hipEvent_t ev_send[XMAXH] = {}, ev_xfer[XMAXH] = {};
     BlockPlan bplan{};  // KERNEL_BLOCK
+    // gp_summary_take (gp_summary.hip): partial records and gather buffer, allocated at the first call
+    void* sum_scratch = nullptr;
+    size_t sum_scratch_bytes = 0;
 };
 #pragma GCC visibility push(hidden)
 

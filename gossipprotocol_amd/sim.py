@@ -167,6 +167,19 @@ class Simulation:
                                       w.ctypes.data, f.ctypes.data))
         return {"c": c, "s": s, "w": w, "flags": f}
 
+    def summary(self, tol: float = 1e-10, scope: str = "local") -> L.GpSummary:
+        """What the run has computed so far, reduced on the device (gp_summary_take): counts of
+        active / converged nodes, gossip's counter histogram, push-sum's estimate range, largest
+        error, nodes within `tol` of the true average and the conserved sums.  scope "local":
+        the ids this handle owns; "global" (every rank of a multi-process run calls it): the
+        whole network.  Leaves the run untouched."""
+        scopes = {"local": L.GP_SCOPE_LOCAL, "global": L.GP_SCOPE_GLOBAL}
+        if scope not in scopes:
+            raise ValueError(f"scope must be 'local' or 'global' (got {scope!r})")
+        out = L.GpSummary()
+        self._chk(self._L.gp_summary_take(self._h, tol, scopes[scope], C.byref(out)))
+        return out
+
     def kernel_stats(self, reset: bool = False):
         ms, n = C.c_double(), C.c_int64()
         name = C.create_string_buffer(128)
@@ -248,6 +261,13 @@ class Ensemble:
         L.check(self._L.gp_ensemble_read_state(self._h, member, first, count, c.ctypes.data, s.ctypes.data,
                                                w.ctypes.data, f.ctypes.data), self._L)
         return {"c": c, "s": s, "w": w, "flags": f}
+
+    def summary(self, tol: float = 1e-10):
+        """One :class:`GpSummary` per member, in seed order, from one launch (gp_ensemble_summary);
+        each equals ``Simulation(..., seed).summary(tol)`` at the member's round."""
+        out = (L.GpSummary * len(self.seeds))()
+        L.check(self._L.gp_ensemble_summary(self._h, tol, out), self._L)
+        return list(out)
 
 
 def run(num_nodes: int, topology: str, algorithm: str, seed: int = 1, max_rounds: int = 0, device: int = 0):

@@ -204,6 +204,50 @@ int gp_ensemble_read_state(gp_ensemble* e, int64_t member, int64_t first, int64_
                            double* s, double* w, uint8_t* flags);
 void gp_ensemble_destroy(gp_ensemble* e);
 
+/* ---- State summary: what a run computed, reduced on the device ---
+ * The reference never printed s/w, yet that ratio is the whole
+ * output of push-sum.  gp_summary_take reduces the node state where it lives, in
+ * one pass (17 B per push-sum node, 4 B per gossip node), instead of copying it
+ * to the host with gp_read_state.  Every field is a pure function of the state:
+ * two calls on the same handle and state return identical bytes. */
+enum { GP_SCOPE_LOCAL = 0, GP_SCOPE_GLOBAL = 1 };
+typedef struct gp_summary {      /* blittable, fixed layout (304 bytes) */
+    int64_t first, count;        /* node ids covered: [first, first + count) */
+    int64_t population, rounds;  /* P of the whole network; rounds executed when the summary was taken */
+    int32_t algorithm, reserved; /* GP_GOSSIP | GP_PUSHSUM; 0 */
+    int64_t active, converged;   /* nodes with flag bit0 / bit1 set, as gp_read_state defines them */
+    /* gossip (all zero for push-sum) */
+    int64_t c_hist[12];          /* nodes whose rumour counter c is 0..10, and (last) c >= 11 */
+    int32_t c_max, reserved2;    /* largest rumour counter; 0 */
+    /* push-sum (all zero for gossip) */
+    int64_t cnt_hist[4];         /* nodes whose stability count (flag bits 2-3) is 0..3 */
+    double  est_min, est_max;    /* min / max over the nodes of the estimate fl(s / w) */
+    double  w_min, w_max;        /* min / max weight */
+    double  err_max;             /* max |e|, e = fl(fl(s / w) - mu), mu = (P - 1) / 2 (the true average) */
+    int64_t err_max_node;        /* lowest node id attaining err_max */
+    int64_t within_tol;          /* nodes with |e| <= tol */
+    double  tol;                 /* the tolerance the summary was taken with */
+    double  sum_s[2], sum_w[2];  /* sum of s / of w as a double-double (hi, lo): the conserved mass */
+    double  sum_sqerr[2];        /* sum of fl(e * e), double-double (hi, lo) */
+} gp_summary;
+
+/* Summary of the node ids `scope` covers.  GP_SCOPE_LOCAL: the ids this handle owns
+ * (a single-GPU or virtual-rank handle owns all P; a gp_create_rank handle its slab).
+ * GP_SCOPE_GLOBAL on a gp_create_rank handle is collective -- every rank calls it, the
+ * ranks' local summaries are gathered over the handle's communicator and merged in rank
+ * order, and every rank receives the whole network's summary; on any other handle it
+ * equals LOCAL.  tol must be finite and >= 0.  Synchronises the handle's stream, reads
+ * the state gp_read_state would read, and leaves the run untouched. */
+int gp_summary_take(gp_sim* sim, double tol, int32_t scope, gp_summary* out);
+/* out = a joined with b (host only, no GPU).  a and b must be adjacent
+ * (a.first + a.count == b.first) and agree in population, rounds, algorithm and tol,
+ * else GP_EINVAL.  Counts and histograms add, min / max combine, err_max_node ties go
+ * to the lower id, the double-double sums add as double-doubles.  out may alias a or b. */
+int gp_summary_merge(const gp_summary* a, const gp_summary* b, gp_summary* out);
+/* One summary per ensemble member into out (nseeds records, each with first = 0 and
+ * count = P, rounds = the member's), in one launch. */
+int gp_ensemble_summary(gp_ensemble* e, double tol, gp_summary* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """Convergence statistics over many seeds with ensemble runs.
 
-    python tools/ensemble_stats.py --nodes 100 200 ... 1000 --seeds 256 [--sequential] [--out DIR]
+    python tools/ensemble_stats.py --nodes 100 200 ... 1000 --seeds 256 [--sequential] [--summary] [--out DIR]
 
 For every topology x algorithm pair and node count one ensemble (gossipprotocol_amd.Ensemble:
 one workgroup per seed, all seeds at once) is run to convergence; the tool prints the median
@@ -12,6 +12,9 @@ time divided by the slowest member's rounds, i.e. what one round costs inside th
 --sequential also runs the same members one by one through Simulation (create, run,
 destroy per seed: what a seed cost before ensembles), checks that both paths report the
 same rounds for every seed, and prints the ratio of members per second.
+
+--summary adds, per (n, pair), the median and the maximum over the seeds of the members' err_max
+(Ensemble.summary: the largest |s / w - (P - 1) / 2| of a member when it stopped; 0 for gossip).
 """
 import argparse
 import json
@@ -31,7 +34,7 @@ def quantile(sorted_vals, q):
     return sorted_vals[k]
 
 
-def run_ensemble(n, topo, alg, seeds, max_rounds, device):
+def run_ensemble(n, topo, alg, seeds, max_rounds, device, summary=False):
     from gossipprotocol_amd import Ensemble
     from gossipprotocol_amd import _lib as L
     t0 = time.perf_counter()
@@ -39,9 +42,12 @@ def run_ensemble(n, topo, alg, seeds, max_rounds, device):
         t1 = time.perf_counter()
         recs = ens.run()
         t2 = time.perf_counter()
+        errs = [m.err_max for m in ens.summary()] if summary else None  # (outside the timed run)
     t3 = time.perf_counter()
     rounds = [int(r.rounds) for r in recs]
     conv = sum(r.status == L.GP_STATUS_CONVERGED for r in recs)
+    if summary:
+        return rounds, conv, (t3 - t0) * 1e3, (t2 - t1) * 1e3, errs
     return rounds, conv, (t3 - t0) * 1e3, (t2 - t1) * 1e3
 
 
@@ -64,6 +70,7 @@ def main():
     ap.add_argument("--max-rounds", type=int, default=10**6)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--sequential", action="store_true", help="also run every member alone through Simulation")
+    ap.add_argument("--summary", action="store_true", help="add the median / max over seeds of the members' err_max")
     ap.add_argument("--out", default=None, help="directory for ensemble_stats.json")
     a = ap.parse_args()
     seeds = list(range(1, a.seeds + 1))
@@ -75,6 +82,8 @@ def main():
 
     head = f"{'algorithm':9s} {'topology':8s} {'n':>6s} {'median':>8s} {'q05':>8s} {'q95':>8s} {'max':>8s} " \
            f"{'conv':>9s} {'wall ms':>9s} {'round us':>9s}"
+    if a.summary:
+        head += f" {'err med':>10s} {'err max':>10s}"
     if a.sequential:
         head += f" {'seq ms':>10s} {'speedup':>8s}"
     print(head, flush=True)
@@ -82,7 +91,8 @@ def main():
     for alg in a.algorithms:
         for topo in a.topologies:
             for n in a.nodes:
-                rounds, conv, wall_ms, run_ms = run_ensemble(n, topo, alg, seeds, a.max_rounds, a.device)
+                rounds, conv, wall_ms, run_ms, *errs = run_ensemble(n, topo, alg, seeds, a.max_rounds, a.device,
+                                                                    summary=a.summary)
                 srt = sorted(rounds)
                 row = {"algorithm": alg, "topology": topo, "n": n, "members": len(seeds), "rounds": rounds,
                        "median_rounds": quantile(srt, 0.5), "q05_rounds": quantile(srt, 0.05),
@@ -93,6 +103,10 @@ def main():
                 line = f"{alg:9s} {topo:8s} {n:6d} {row['median_rounds']:8d} {row['q05_rounds']:8d} " \
                        f"{row['q95_rounds']:8d} {srt[-1]:8d} {conv:5d}/{len(seeds):<3d} {wall_ms:9.2f} " \
                        f"{row['round_us']:9.3f}"
+                if a.summary:
+                    es = sorted(errs[0])
+                    row["err_max_median"], row["err_max_max"] = quantile(es, 0.5), es[-1]
+                    line += f" {row['err_max_median']:10.3e} {es[-1]:10.3e}"
                 if a.sequential:
                     seq_rounds, seq_ms = run_sequential(n, topo, alg, seeds, a.max_rounds, a.device)
                     if seq_rounds != rounds:
