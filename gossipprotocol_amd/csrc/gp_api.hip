@@ -524,7 +524,14 @@ int gp_kernel_stats(gp_sim* s, double* total_ms, int64_t* launches, char* name, 
     }
     if (total_ms) *total_ms = s->kernel_ms;
     if (launches) *launches = s->launches;
-    if (name && name_cap > 0) std::snprintf(name, (size_t)name_cap, "%s", bulk_kernel_name(s->slab[0].S));
+    if (name && name_cap > 0) {
+        const DevState& S = s->slab[0].S;
+        // (GP_GRID, experiments: the grid the tiled round kernels run on after the name, as
+        // k_ps_tile<IMP3D>@8 -- the tests' proof that the override reached choose_kernel)
+        if (exp_env("GP_GRID") && S.kernel == KERNEL_TILE && S.topo != FULL)
+            std::snprintf(name, (size_t)name_cap, "%s@%d", bulk_kernel_name(S), s->grid);
+        else std::snprintf(name, (size_t)name_cap, "%s", bulk_kernel_name(S));
+    }
     if (reset) {
         s->kernel_ms = 0.0;
         s->launches = 0;

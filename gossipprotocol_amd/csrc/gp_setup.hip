@@ -190,8 +190,9 @@ uint32_t round_regions(const gp_sim* s, int kernel, uint32_t walk) {
 }
 
 // Kernel variant and grid for this run (measured defaults; GP_KERNEL / GP_XSEGS / GP_WALK /
-// GP_WX / GP_WIDE override them in the experiments build).
-void choose_kernel(gp_sim* s, int64_t nloc_max, int& kernel, uint32_t& col_xsegs, uint32_t& walk, uint32_t& wx,
+// GP_WX / GP_WIDE / GP_GRID override them in the experiments build).  GP_EINVAL: a GP_GRID the
+// run cannot take.
+int choose_kernel(gp_sim* s, int64_t nloc_max, int& kernel, uint32_t& col_xsegs, uint32_t& walk, uint32_t& wx,
                    uint32_t& wide) {
     hipDeviceProp_t prop;
     (void)hipGetDeviceProperties(&prop, s->device);
@@ -274,6 +275,28 @@ void choose_kernel(gp_sim* s, int64_t nloc_max, int& kernel, uint32_t& col_xsegs
         if (res >= 8) s->grid = (int)std::min<int64_t>(s->grid, res);
         else walk = 2;
     }
+    // GP_GRID (experiments; tests/test_gpu_tile_sequence.py): fewer blocks for the tiled round
+    // kernels than the rule above gives, so that a block walks several tiles of a small slab and
+    // carries its prefetches, its claims and its LDS from one tile to the next -- which the rule
+    // allows only from ~1.7e7 nodes on.  It only lowers the grid: everything else launched with
+    // it (k_init, k_rbits_init, the set-up, pack, injector and recount kernels) strides over its
+    // range by the grid, and the round kernels' walks and round close take any grid.  A value
+    // that is no number, below 1 or above the grid chosen is an error, so a test cannot run the
+    // default grid unnoticed; region rounds take multiples of 8 only (launch_round_tile_region)
+    // and ignore any other value.
+    if (const char* e = exp_env("GP_GRID")) {
+        if (kernel == KERNEL_TILE && cfg->topology != GP_FULL) {
+            char* end = nullptr;
+            errno = 0;
+            const long v = std::strtol(e, &end, 10);
+            if (errno || end == e || *end != '\0' || v < 1 || v > (long)s->grid) {
+                set_err("GP_GRID=%s: not a grid of 1..%d blocks", e, s->grid);
+                return GP_EINVAL;
+            }
+            if (round_regions(s, kernel, walk) <= 1 || v % 8 == 0) s->grid = (int)v;
+        }
+    }
+    return GP_OK;
 }
 
 // Everything after the handle exists: slabs, topology, initial state, round 0.
@@ -284,7 +307,7 @@ int build_sim(gp_sim* s) {
     for (int w = 0; w < s->world; ++w) nloc_max = std::max<int64_t>(nloc_max, s->bounds[w + 1] - s->bounds[w]);
     int kernel;
     uint32_t col_xsegs, walk, wx, wide;
-    choose_kernel(s, nloc_max, kernel, col_xsegs, walk, wx, wide);
+    if ((rc = choose_kernel(s, nloc_max, kernel, col_xsegs, walk, wx, wide))) return rc;
     const uint32_t rreg = round_regions(s, kernel, walk);
     if (s->mode == MODE_VIRTUAL) {
         s->slab.resize(s->world);

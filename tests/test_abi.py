@@ -110,11 +110,12 @@ def test_product_library_has_no_environment_switches():
     for knob in (b"GP_KERNEL", b"GP_XSEGS", b"GP_WALK", b"GP_WX", b"GP_STAGE_CAP", b"GP_NO_PACK",
                  b"GP_FORCE_RCCL", b"GP_XCAP", b"GP_WIDE", b"GP_RQ8", b"GP_CHECK_CLOSE", b"GP_FUSE",
                  b"GP_RREGIONS", b"GP_FB_FUSED", b"GP_IND4_WIDE", b"GP_FB_CAP1", b"GP_FB_CAP2", b"GP_XREGIONS",
-                 b"GP_HALO_CAP"):
+                 b"GP_HALO_CAP", b"GP_GRID"):
         assert knob not in prod, knob
         assert knob in exp, knob
     # overrides of variants measured and rejected are gone from both builds (round 6; GP_XREGIONS is
-    # back as a test override that accepts only the eight regions the product itself uses)
+    # back as a test override that accepts only the eight regions the product itself uses, GP_GRID as
+    # one that only lowers the tiled round kernels' grid: tests/test_gpu_tile_sequence.py)
     for knob in (b"GP_PSTREAM", b"GP_XHALVES", b"GP_HALO_FULL", b"GP_RLAST", b"GP_FB_S1D",
-                 b"GP_FOLD_BLOCKS", b"GP_GRID"):
+                 b"GP_FOLD_BLOCKS"):
         assert knob not in prod and knob not in exp, knob
