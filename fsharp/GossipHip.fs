@@ -94,6 +94,30 @@ extern int gp_ensemble_read_state(nativeint ensemble, int64 ``member``, int64 fi
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern void gp_ensemble_destroy(nativeint ensemble)
 
+// Ensembles with a failure model: crashed nodes and lost messages (SRS v1-F, DESIGN.md §11)
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type GpFaults =
+    val mutable NodeFail: double
+    val mutable MsgDrop: double
+    val mutable FailRound: int64
+    val mutable Reserved: int64
+
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type GpFaultStats =
+    val mutable Doomed: int64
+    val mutable Down: int64
+    val mutable Threshold: int64
+    val mutable Lost: int64
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int64 gp_ensemble_faults_max_nodes(int topology, int algorithm)
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gp_ensemble_create_faults(GpConfig& cfg, GpFaults& faults, uint64[] seeds, int64 nseeds, nativeint& ensemble)
+
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gp_ensemble_fault_stats(nativeint ensemble, [<Out>] GpFaultStats[] stats)
+
 // State summary: what a run computed, reduced on the device (INTEGRATION.md §2.3).
 // gp_summary is 304 bytes; the fixed arrays are spelled out field by field to stay blittable.
 [<Struct; StructLayout(LayoutKind.Sequential)>]

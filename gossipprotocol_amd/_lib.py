@@ -22,6 +22,7 @@ GP_STATUS_CONVERGED, GP_STATUS_MAX_ROUNDS, GP_STATUS_RUNNING = 0, 1, 2
 GP_FLAG_KERNEL_TIMING = 1
 GP_FLAG_VIRTUAL_RANKS = 2
 GP_SCOPE_LOCAL, GP_SCOPE_GLOBAL = 0, 1
+GP_STATE_DOWN = 0x10  # gp_ensemble_read_state flag bit 4 (failure ensembles)
 ERRORS = {-1: "GP_EINVAL", -2: "GP_ENOMEM", -3: "GP_EHIP", -4: "GP_ENCCL", -5: "GP_ESTATE", -6: "GP_ENODEV"}
 
 
@@ -49,6 +50,17 @@ class GpMember(C.Structure):
     """One ensemble member (gp_member)."""
     _fields_ = [("seed", C.c_uint64), ("rounds", C.c_int64), ("converged", C.c_int64),
                 ("seed_node", C.c_int64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GpFaults(C.Structure):
+    """Failure model of an ensemble (gp_faults)."""
+    _fields_ = [("node_fail", C.c_double), ("msg_drop", C.c_double), ("fail_round", C.c_int64),
+                ("reserved", C.c_int64)]
+
+
+class GpFaultStats(C.Structure):
+    """Per-member failure statistics (gp_fault_stats)."""
+    _fields_ = [("doomed", C.c_int64), ("down", C.c_int64), ("threshold", C.c_int64), ("lost", C.c_int64)]
 
 
 class GpSummary(C.Structure):
@@ -112,6 +124,10 @@ SIGNATURES = [
     ("gp_ensemble_members", _i32, [_vp, C.POINTER(GpMember)]),
     ("gp_ensemble_read_state", _i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("gp_ensemble_destroy", None, [_vp]),
+    ("gp_ensemble_faults_max_nodes", _i64, [_i32, _i32]),
+    ("gp_ensemble_create_faults", _i32, [C.POINTER(GpConfig), C.POINTER(GpFaults), C.POINTER(C.c_uint64), _i64,
+                                         C.POINTER(_vp)]),
+    ("gp_ensemble_fault_stats", _i32, [_vp, C.POINTER(GpFaultStats)]),
     ("gp_summary_take", _i32, [_vp, C.c_double, _i32, C.POINTER(GpSummary)]),
     ("gp_summary_merge", _i32, [C.POINTER(GpSummary), C.POINTER(GpSummary), C.POINTER(GpSummary)]),
     ("gp_ensemble_summary", _i32, [_vp, C.c_double, C.POINTER(GpSummary)]),

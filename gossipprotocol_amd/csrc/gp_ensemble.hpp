@@ -14,7 +14,8 @@ namespace gp {
 constexpr int ENS_THREADS = 1024;            // largest workgroup
 constexpr int ENS_NPT_MAX = 8;               // push-sum: node slots a thread keeps in registers
 constexpr uint32_t ENS_LDS_MAX = 150 * 1024; // dynamic LDS a member may ask for (a CU has 160 KiB)
-constexpr uint32_t ENS_LDS_HDR = 16;         // [0] cumulative alerts, [1] injector live count
+constexpr uint32_t ENS_LDS_HDR = 16;         // [0] cumulative alerts, [1] injector live count;
+                                             // failure kernels: [2] |D|, [3] messages lost in this launch
 constexpr uint32_t ENS_NONE = 0xFFFFu;       // end of a receiver's message list (node ids are < 0xFFFF)
 
 constexpr uint32_t ens_up8(uint32_t b) { return (b + 7u) & ~7u; }
@@ -25,7 +26,10 @@ constexpr uint32_t ens_up8(uint32_t b) { return (b + 7u) & ~7u; }
 //              (full, Imp3D: per-receiver list of this round's random-edge senders), rnd u16[P] (Imp3D),
 //              dir u8[P] (not full)
 // The per-node (s, w, flags) of push-sum live in registers (ENS_NPT_MAX slots per thread).
-constexpr uint32_t ens_lds_bytes(int topo, int alg, uint32_t P) {
+// The failure kernels (SRS v1-F, gp_ensemble_faults.hip) append
+//   doomed bitmap u32[ceil(P/32)]: bit i set iff node i is in D
+// to either image, redrawn from the seed at the start of every launch.
+constexpr uint32_t ens_lds_bytes(int topo, int alg, uint32_t P, bool faults = false) {
     uint32_t b = ENS_LDS_HDR;
     if (alg == GOSSIP) {
         b += ens_up8(4 * P) * 2;
@@ -37,22 +41,25 @@ constexpr uint32_t ens_lds_bytes(int topo, int alg, uint32_t P) {
         if (topo == IMP3D) b += ens_up8(2 * P);
         if (topo != FULL) b += ens_up8(P);
     }
+    if (faults) b += ens_up8(4 * ((P + 31) / 32));
     return b;
 }
 
 // Largest population a member may have: the LDS image fits and every node has a
 // thread slot.  A compile-time function of the layout above.
-constexpr uint32_t ens_max_population(int topo, int alg) {
+constexpr uint32_t ens_max_population(int topo, int alg, bool faults = false) {
     uint32_t P = (uint32_t)ENS_THREADS * ENS_NPT_MAX;
-    while (P > 2 && ens_lds_bytes(topo, alg, P) > ENS_LDS_MAX) --P;
+    while (P > 2 && ens_lds_bytes(topo, alg, P, faults) > ENS_LDS_MAX) --P;
     return P;
 }
 static_assert(ens_max_population(IMP3D, PUSHSUM) >= 1001 && ens_max_population(FULL, PUSHSUM) >= 1001, "report range");
+static_assert(ens_max_population(IMP3D, PUSHSUM, true) >= 1001 && ens_max_population(FULL, PUSHSUM, true) >= 1001,
+              "report range, failure layout");
 static_assert((uint32_t)ENS_THREADS * ENS_NPT_MAX < ENS_NONE, "node ids must fit the 16-bit list links");
 
 // Largest num_nodes: line / full P = n + 1; 3D / Imp3D the largest whole cube.
-constexpr int64_t ens_max_nodes(int topo, int alg) {
-    const uint32_t P = ens_max_population(topo, alg);
+constexpr int64_t ens_max_nodes(int topo, int alg, bool faults = false) {
+    const uint32_t P = ens_max_population(topo, alg, faults);
     if (topo == LINE || topo == FULL) return (int64_t)P - 1;
     uint32_t g = 1;
     while ((g + 1) * (g + 1) * (g + 1) <= P) ++g;
@@ -76,9 +83,36 @@ struct EnsArgs {
     int64_t max_rounds;  // cap on a member's total rounds
 };
 
+// Failure model (SRS v1-F): Philox streams and the per-member record
+// that persists between launches beside gp_member (whose `converged` carries the
+// counted alerts).  D itself is never stored: a pure function of the seed.
+constexpr uint32_t S_FAULT_NODE = 5, S_FAULT_DROP = 6;
+struct EnsFaultRec {
+    int64_t lost;    // messages sent that nobody received, all launches so far
+    int64_t doomed;  // |D|
+};
+// Arguments of the failure kernels: the plain ones plus the failure parameters.  An
+// event with threshold q happens iff (uint64) x < q, x the first Philox output word.
+struct EnsFaultArgs {
+    EnsArgs a;
+    EnsFaultRec* frec;
+    uint64_t q_node, q_drop;  // floor(p * 2^32); 2^32 = always
+    int64_t fail_round;
+};
+
+// Node i in D?  (host: gp_ensemble_read_state; device: the bitmap redraw)
+GP_HD bool ens_doomed(uint32_t k0, uint32_t k1, uint32_t i, uint32_t seed_node, uint64_t q_node) {
+    uint32_t x, y;
+    philox2(i, 0, S_FAULT_NODE, k0, k1, x, y);
+    return i != seed_node && (uint64_t)x < q_node;
+}
+
 // Raises the kernel's dynamic-LDS limit for population P; once per handle.
 hipError_t ens_setup(int topo, int alg, uint32_t P);
 // Plain launch, one workgroup per listed member.
 hipError_t ens_launch(int topo, int alg, const EnsArgs& a, uint32_t nblocks, hipStream_t st);
+// The same two for the failure kernels (gp_ensemble_faults.hip).
+hipError_t ens_faults_setup(int topo, int alg, uint32_t P);
+hipError_t ens_faults_launch(int topo, int alg, const EnsFaultArgs& a, uint32_t nblocks, hipStream_t st);
 
 }  // namespace gp

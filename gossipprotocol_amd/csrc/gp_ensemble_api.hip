@@ -21,6 +21,9 @@ namespace {
 // least one workgroup), the workgroups run in waves, so the chunk shrinks by the
 // number of waves, down to a floor of 256 rounds, below which the launch overhead
 // (~10 us and the record copy) would show.
+// The failure kernels keep the constant: measured at their own caps,
+// 256 members, the slowest round is 43.5 us (Imp3D push-sum, 5832 nodes), so 8192
+// rounds are at most 0.36 s.
 constexpr int64_t ENS_LAUNCH_ROUNDS = 8192;
 constexpr int64_t ENS_LAUNCH_ROUNDS_MIN = 256;
 constexpr int64_t ENS_CUS = 256;
@@ -53,6 +56,20 @@ int64_t max_nodes(int topo, int alg) {
     return table[topo][alg];
 }
 
+// The same for the failure layout (the doomed bitmap lowers the LDS-bound caps).
+int64_t faults_max_nodes(int topo, int alg) {
+    static constexpr int64_t table[4][2] = {
+        {ens_max_nodes(LINE, GOSSIP, true), ens_max_nodes(LINE, PUSHSUM, true)},
+        {ens_max_nodes(FULL, GOSSIP, true), ens_max_nodes(FULL, PUSHSUM, true)},
+        {ens_max_nodes(GRID3D, GOSSIP, true), ens_max_nodes(GRID3D, PUSHSUM, true)},
+        {ens_max_nodes(IMP3D, GOSSIP, true), ens_max_nodes(IMP3D, PUSHSUM, true)},
+    };
+    return table[topo][alg];
+}
+
+// p in [0, 1] -> q = floor(p * 2^32), exact in double; an event happens iff x < q.
+uint64_t fault_threshold(double p) { return (uint64_t)std::floor(p * 4294967296.0); }
+
 }  // namespace
 
 struct gp_ensemble {
@@ -67,6 +84,12 @@ struct gp_ensemble {
     std::vector<gp_member> rec;    // host copy of the member records, refreshed after every launch
     std::vector<uint32_t> running; // unfinished members, in member order
     SumAcc* d_sum = nullptr;       // gp_ensemble_summary: one record per member, allocated at the first call
+    // failure model (gp_ensemble_create_faults; SRS v1-F)
+    bool faults = false;
+    gp_faults fp{};
+    uint64_t q_node = 0, q_drop = 0;
+    EnsFaultRec* d_frec = nullptr;
+    std::vector<EnsFaultRec> frec;  // host copy, refreshed after every launch
 };
 
 namespace {
@@ -92,7 +115,19 @@ int launch(gp_ensemble* e, int64_t nrounds, bool init) {
     HIP_TRY(hipMemcpyAsync(e->d_idx, e->running.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     e->args.nrounds = nrounds;
     e->args.init = init ? 1 : 0;
-    HIP_TRY(ens_launch(e->cfg.topology, e->cfg.algorithm, e->args, (uint32_t)n, e->stream));
+    if (e->faults) {
+        EnsFaultArgs f{};
+        f.a = e->args;
+        f.frec = e->d_frec;
+        f.q_node = e->q_node;
+        f.q_drop = e->q_drop;
+        f.fail_round = e->fp.fail_round;
+        HIP_TRY(ens_faults_launch(e->cfg.topology, e->cfg.algorithm, f, (uint32_t)n, e->stream));
+        HIP_TRY(hipMemcpyAsync(e->frec.data(), e->d_frec, e->frec.size() * sizeof(EnsFaultRec), hipMemcpyDeviceToHost,
+                                   e->stream));
+    } else {
+        HIP_TRY(ens_launch(e->cfg.topology, e->cfg.algorithm, e->args, (uint32_t)n, e->stream));
+    }
     HIP_TRY(hipMemcpyAsync(e->rec.data(), e->args.rec, e->rec.size() * sizeof(gp_member), hipMemcpyDeviceToHost,
                                e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -108,9 +143,13 @@ int create(gp_ensemble* e, const uint64_t* seeds) {
     const size_t n = (size_t)e->nseeds, P = (size_t)e->P;
     HIP_TRY(hipSetDevice(e->cfg.device));
     HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    HIP_TRY(ens_setup(topo, alg, (uint32_t)P));
+    HIP_TRY(e->faults ? ens_faults_setup(topo, alg, (uint32_t)P) : ens_setup(topo, alg, (uint32_t)P));
     EnsArgs& a = e->args;
     int rc = ens_alloc(e, &a.rec, n);
+    if (!rc && e->faults) {
+        rc = ens_alloc(e, &e->d_frec, n);
+        e->frec.assign(n, EnsFaultRec{});  // (the set-up launch writes every record)
+    }
     if (!rc) rc = ens_alloc(e, &e->d_idx, n);
     if (alg == GP_GOSSIP) {
         if (!rc) rc = ens_alloc(e, &a.c, n * P);
@@ -151,12 +190,9 @@ int64_t gp_ensemble_max_nodes(int32_t topology, int32_t algorithm) {
     return max_nodes(topology, algorithm);
 }
 
-int gp_ensemble_create(const gp_config* cfg, const uint64_t* seeds, int64_t nseeds, gp_ensemble** out) {
-    if (!cfg || !out) {
-        set_err("gp_ensemble_create: null argument");
-        return GP_EINVAL;
-    }
-    *out = nullptr;
+// gp_ensemble_create and gp_ensemble_create_faults (faults != null, already checked).
+static int ensemble_create(const gp_config* cfg, const gp_faults* faults, const uint64_t* seeds, int64_t nseeds,
+                           gp_ensemble** out) {
     if (!seeds) {
         set_err("gp_ensemble_create: seeds is null");
         return GP_EINVAL;
@@ -180,10 +216,10 @@ int gp_ensemble_create(const gp_config* cfg, const uint64_t* seeds, int64_t nsee
         set_err("gp_ensemble_create: a population of %lld has no edge", (long long)P);
         return GP_EINVAL;
     }
-    const int64_t cap = max_nodes(cfg->topology, cfg->algorithm);
+    const int64_t cap = faults ? faults_max_nodes(cfg->topology, cfg->algorithm) : max_nodes(cfg->topology, cfg->algorithm);
     if (cfg->num_nodes > cap) {
-        set_err("gp_ensemble_create: num_nodes %lld exceeds the ensemble cap %lld of this pair (one workgroup's LDS); "
-                "use gp_create", (long long)cfg->num_nodes, (long long)cap);
+        set_err("gp_ensemble_create: num_nodes %lld exceeds the ensemble cap %lld of this pair (one workgroup's LDS%s); "
+                "use gp_create", (long long)cfg->num_nodes, (long long)cap, faults ? ", failure layout" : "");
         return GP_EINVAL;
     }
     const int rc_dev = check_device(cfg->device);
@@ -200,12 +236,81 @@ int gp_ensemble_create(const gp_config* cfg, const uint64_t* seeds, int64_t nsee
     e->g = g;
     e->nseeds = nseeds;
     e->nwords = (uint32_t)((T + 31) / 32);
+    if (faults) {
+        e->faults = true;
+        e->fp = *faults;
+        e->q_node = fault_threshold(faults->node_fail);
+        e->q_drop = fault_threshold(faults->msg_drop);
+    }
     const int rc = create(e, seeds);
     if (rc) {
         gp_ensemble_destroy(e);  // (hipFree does not touch the error message)
         return rc;
     }
     *out = e;
+    return GP_OK;
+}
+
+int gp_ensemble_create(const gp_config* cfg, const uint64_t* seeds, int64_t nseeds, gp_ensemble** out) {
+    if (!cfg || !out) {
+        set_err("gp_ensemble_create: null argument");
+        return GP_EINVAL;
+    }
+    *out = nullptr;
+    return ensemble_create(cfg, nullptr, seeds, nseeds, out);
+}
+
+int64_t gp_ensemble_faults_max_nodes(int32_t topology, int32_t algorithm) {
+    if (!pair_ok(topology, algorithm)) return GP_EINVAL;
+    return faults_max_nodes(topology, algorithm);
+}
+
+int gp_ensemble_create_faults(const gp_config* cfg, const gp_faults* faults, const uint64_t* seeds, int64_t nseeds,
+                              gp_ensemble** out) {
+    if (!cfg || !out) {
+        set_err("gp_ensemble_create_faults: null argument");
+        return GP_EINVAL;
+    }
+    *out = nullptr;
+    if (!faults) {
+        set_err("gp_ensemble_create_faults: faults is null");
+        return GP_EINVAL;
+    }
+    // (the negated comparisons also refuse NaN)
+    if (!(faults->node_fail >= 0.0 && faults->node_fail <= 1.0)) {
+        set_err("gp_ensemble_create_faults: node_fail must be in [0, 1] (got %g)", faults->node_fail);
+        return GP_EINVAL;
+    }
+    if (!(faults->msg_drop >= 0.0 && faults->msg_drop <= 1.0)) {
+        set_err("gp_ensemble_create_faults: msg_drop must be in [0, 1] (got %g)", faults->msg_drop);
+        return GP_EINVAL;
+    }
+    if (faults->fail_round < 0) {
+        set_err("gp_ensemble_create_faults: fail_round must be >= 0 (got %lld)", (long long)faults->fail_round);
+        return GP_EINVAL;
+    }
+    if (faults->reserved != 0) {
+        set_err("gp_ensemble_create_faults: reserved must be 0 (got %lld)", (long long)faults->reserved);
+        return GP_EINVAL;
+    }
+    return ensemble_create(cfg, faults, seeds, nseeds, out);
+}
+
+int gp_ensemble_fault_stats(gp_ensemble* e, gp_fault_stats* out) {
+    if (!e || !out) {
+        set_err("gp_ensemble_fault_stats: null argument");
+        return GP_EINVAL;
+    }
+    for (int64_t m = 0; m < e->nseeds; ++m) {
+        gp_fault_stats& o = out[m];
+        o = gp_fault_stats{0, 0, e->T, 0};
+        if (!e->faults) continue;
+        const EnsFaultRec& f = e->frec[(size_t)m];
+        o.doomed = f.doomed;
+        o.down = e->rec[(size_t)m].rounds >= e->fp.fail_round ? f.doomed : 0;
+        o.threshold = std::max<int64_t>(1, e->T - f.doomed);
+        o.lost = f.lost;
+    }
     return GP_OK;
 }
 
@@ -263,6 +368,14 @@ int gp_ensemble_read_state(gp_ensemble* e, int64_t member, int64_t first, int64_
     if (count == 0) return GP_OK;
     HIP_TRY(hipSetDevice(e->cfg.device));
     const size_t at = (size_t)member * (size_t)e->P + (size_t)first, n = (size_t)count;
+    // Failure ensembles: is node first + q down at the member's round count?  D is a pure
+    // function of the seed, recomputed here with the kernels' own draw.
+    const gp_member& mr = e->rec[(size_t)member];
+    const bool any_down = e->faults && mr.rounds >= e->fp.fail_round;
+    auto down = [&](size_t q) {
+        return any_down && ens_doomed((uint32_t)mr.seed, (uint32_t)(mr.seed >> 32), (uint32_t)(first + (int64_t)q),
+                                      (uint32_t)mr.seed_node, e->q_node);
+    };
     if (e->cfg.algorithm == GP_GOSSIP) {
         std::vector<int32_t> hc(n);
         HIP_TRY(hipMemcpyAsync(hc.data(), e->args.c + at, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
@@ -276,6 +389,7 @@ int gp_ensemble_read_state(gp_ensemble* e, int64_t member, int64_t first, int64_
             if (flags) {
                 const int act = ((int64_t)(first + (int64_t)q) == seed_node || ci >= 1) && ci <= 10;
                 flags[q] = (uint8_t)(act | ((ci >= (int32_t)GOSSIP_DONE) << 1));
+                if (down(q)) flags[q] = (uint8_t)((flags[q] & ~1u) | GP_STATE_DOWN);  // a down node is not active
             }
         }
     } else {
@@ -283,6 +397,9 @@ int gp_ensemble_read_state(gp_ensemble* e, int64_t member, int64_t first, int64_
         if (w) HIP_TRY(hipMemcpyAsync(w, e->args.w + at, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
         if (flags) HIP_TRY(hipMemcpyAsync(flags, e->args.fl + at, n, hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
+        if (flags && any_down)
+            for (size_t q = 0; q < n; ++q)
+                if (down(q)) flags[q] |= GP_STATE_DOWN;  // (its active bit stays frozen as it was)
         if (c) std::fill(c, c + n, 0);
     }
     return GP_OK;

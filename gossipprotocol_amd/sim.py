@@ -190,18 +190,35 @@ class Simulation:
         return self._L.gp_alg_bytes_per_node(self._h)
 
 
-def ensemble_max_nodes(topology: str, algorithm: str) -> int:
-    """Largest num_nodes an :class:`Ensemble` accepts for the pair (host only)."""
-    return L.check(L.lib().gp_ensemble_max_nodes(parse_topology(topology), parse_algorithm(algorithm)))
+def ensemble_max_nodes(topology: str, algorithm: str, faults: bool = False) -> int:
+    """Largest num_nodes an :class:`Ensemble` accepts for the pair (host only); faults=True:
+    the cap of an ensemble with a failure model."""
+    f = L.lib().gp_ensemble_faults_max_nodes if faults else L.lib().gp_ensemble_max_nodes
+    return L.check(f(parse_topology(topology), parse_algorithm(algorithm)))
+
+
+class Faults:
+    """Failure model of an :class:`Ensemble` (gp_faults; SRS v1-F): every
+    node but the seed node is doomed with probability ``node_fail`` and down -- silent, deaf,
+    frozen -- from round ``fail_round`` on; every node-to-node message is lost with
+    probability ``msg_drop``."""
+
+    def __init__(self, node_fail: float = 0.0, msg_drop: float = 0.0, fail_round: int = 0):
+        self.node_fail, self.msg_drop, self.fail_round = float(node_fail), float(msg_drop), int(fail_round)
+
+    def __repr__(self):
+        return f"Faults(node_fail={self.node_fail}, msg_drop={self.msg_drop}, fail_round={self.fail_round})"
 
 
 class Ensemble:
     """Many small networks at once on one MI355X, one per seed (handle over
     gp_ensemble): the regime of the reference's published curves, n = 100..1000
     (README.md, Report.pdf).  Each member is one workgroup with its state in LDS and
-    is bit-identical to ``Simulation(num_nodes, topology, algorithm, seed)``."""
+    is bit-identical to ``Simulation(num_nodes, topology, algorithm, seed)``.  With
+    ``faults=Faults(...)`` nodes crash and messages get lost (gp_ensemble_create_faults)."""
 
-    def __init__(self, num_nodes: int, topology: str, algorithm: str, seeds, max_rounds: int, device: int = 0):
+    def __init__(self, num_nodes: int, topology: str, algorithm: str, seeds, max_rounds: int, device: int = 0,
+                 faults: "Faults | None" = None):
         self._L = L.lib()
         self.seeds = [int(s) for s in seeds]
         cfg = L.GpConfig()
@@ -215,7 +232,13 @@ class Ensemble:
         self.population = resolve(num_nodes, topology)[0]
         arr = (C.c_uint64 * max(1, len(self.seeds)))(*self.seeds)
         h = C.c_void_p()
-        L.check(self._L.gp_ensemble_create(C.byref(cfg), arr, len(self.seeds), C.byref(h)), self._L)
+        self.faults = faults
+        if faults is None:
+            L.check(self._L.gp_ensemble_create(C.byref(cfg), arr, len(self.seeds), C.byref(h)), self._L)
+        else:
+            f = L.GpFaults(faults.node_fail, faults.msg_drop, faults.fail_round, 0)
+            L.check(self._L.gp_ensemble_create_faults(C.byref(cfg), C.byref(f), arr, len(self.seeds), C.byref(h)),
+                    self._L)
         self._h = h
 
     def close(self):
@@ -261,6 +284,14 @@ class Ensemble:
         L.check(self._L.gp_ensemble_read_state(self._h, member, first, count, c.ctypes.data, s.ctypes.data,
                                                w.ctypes.data, f.ctypes.data), self._L)
         return {"c": c, "s": s, "w": w, "flags": f}
+
+    def fault_stats(self):
+        """One GpFaultStats per member, in seed order: doomed (|D|), down (|D| once the member's
+        rounds reached fail_round), threshold (T_f) and lost (messages nobody received).  A plain
+        ensemble reports zeros and threshold = T."""
+        out = (L.GpFaultStats * len(self.seeds))()
+        L.check(self._L.gp_ensemble_fault_stats(self._h, out), self._L)
+        return list(out)
 
     def summary(self, tol: float = 1e-10):
         """One :class:`GpSummary` per member, in seed order, from one launch (gp_ensemble_summary);

@@ -204,6 +204,47 @@ int gp_ensemble_read_state(gp_ensemble* e, int64_t member, int64_t first, int64_
                            double* s, double* w, uint8_t* flags);
 void gp_ensemble_destroy(gp_ensemble* e);
 
+/* ---- Ensembles with a failure model: SRS v1-F ------
+ * The question the reference never reached: every actor there lives for ever and
+ * every `<!` is delivered.  A failure ensemble fixes, per member, a doomed set D
+ * (node i != seed node is in D with probability node_fail; one Philox draw per
+ * node, stream 5) whose nodes go down from round fail_round on -- they neither send
+ * nor receive, their state is frozen -- and loses every node-to-node message with
+ * probability msg_drop (one draw per sender and round, stream 6; the gossip
+ * injector's messages are never dropped).  Only alerts of nodes outside D count, and
+ * a member converges at T_f = max(1, T - |D|) of them.  A probability p acts as the
+ * threshold q = floor(p * 2^32): an event happens iff the draw's first 32-bit word
+ * is < q, so p = 1 means always and no floating-point comparison decides a fault.
+ * With node_fail = msg_drop = 0 every member is bit-identical to gp_ensemble_create. */
+typedef struct gp_faults {      /* blittable */
+    double node_fail, msg_drop; /* probabilities in [0, 1] */
+    int64_t fail_round;         /* >= 0: the first round in which the doomed nodes are down */
+    int64_t reserved;           /* 0 */
+} gp_faults;
+typedef struct gp_fault_stats { /* one per member, blittable */
+    int64_t doomed;             /* |D| */
+    int64_t down;               /* |D| once the member's rounds >= fail_round, 0 before */
+    int64_t threshold;          /* T_f */
+    int64_t lost;               /* messages a node sent that nobody received: dropped, or addressed
+                                   to a down node (a converged gossip target suppresses, not loses) */
+} gp_fault_stats;
+/* gp_ensemble_read_state flag bit 4: the node is down at the member's current round count
+ * (failure ensembles only; a down gossip node never shows bit 0). */
+enum { GP_STATE_DOWN = 0x10 };
+
+/* gp_ensemble_max_nodes for a failure ensemble (host only): the doomed bitmap takes LDS,
+ * so a cap may be lower than the plain one. */
+int64_t gp_ensemble_faults_max_nodes(int32_t topology, int32_t algorithm);
+/* gp_ensemble_create with a failure model.  Every check of gp_ensemble_create applies
+ * (against gp_ensemble_faults_max_nodes); in addition faults must be non-null, both
+ * probabilities in [0, 1] (NaN refused), fail_round >= 0 and reserved 0, else GP_EINVAL.
+ * The handle works with every gp_ensemble_* call.  gp_member.converged holds the counted
+ * alerts.  gp_ensemble_summary is unchanged: it reduces all P nodes, frozen ones included. */
+int gp_ensemble_create_faults(const gp_config* cfg, const gp_faults* faults, const uint64_t* seeds,
+                              int64_t nseeds, gp_ensemble** out);
+/* nseeds records to out.  On a plain ensemble doomed = down = lost = 0 and threshold = T. */
+int gp_ensemble_fault_stats(gp_ensemble* e, gp_fault_stats* out);
+
 /* ---- State summary: what a run computed, reduced on the device ---
  * The reference never printed s/w, yet that ratio is the whole
  * output of push-sum.  gp_summary_take reduces the node state where it lives, in
