@@ -229,10 +229,9 @@ int gp_create_rank(const gp_config* cfg, int32_t rank, int32_t world, const uint
         set_err("gp_create_rank: bad argument (rank %d, world %d)", rank, world);
         return GP_EINVAL;
     }
-    bool force = false;
     // GP_FORCE_RCCL=1 (experiments): a one-rank RCCL communicator (test of the RCCL transport
     // on a single GPU: init, bookkeeping all-reduce, teardown)
-    if (const char* e = exp_env("GP_FORCE_RCCL")) force = e[0] == '1';
+    const bool force = read_overrides().force_rccl.value_or(false);
     if (world == 1 && !force) return create_common(cfg, MODE_SINGLE, 1, 0, nullptr, out);
     if (!unique_id) {
         set_err("gp_create_rank: null unique id");
@@ -336,7 +335,7 @@ int64_t gp_step(gp_sim* s, int64_t nrounds, int64_t* alerts_out) {
         s->alerts_total = cum;
         s->done = hc.done != 0;
         executed += ex;
-        if (s->mode != MODE_RCCL && exp_env("GP_CHECK_CLOSE")) {  // tests: recount the alerts from the state
+        if (s->mode != MODE_RCCL && s->exp.check_close) {  // (GP_CHECK_CLOSE) tests: recount the alerts from the state
             Scratch tmp;
             unsigned long long* d = nullptr;
             HIP_TRY(tmp.alloc(&d, 1));
@@ -527,8 +526,8 @@ int gp_kernel_stats(gp_sim* s, double* total_ms, int64_t* launches, char* name, 
     if (name && name_cap > 0) {
         const DevState& S = s->slab[0].S;
         // (GP_GRID, experiments: the grid the tiled round kernels run on after the name, as
-        // k_ps_tile<IMP3D>@8 -- the tests' proof that the override reached choose_kernel)
-        if (exp_env("GP_GRID") && S.kernel == KERNEL_TILE && S.topo != FULL)
+        // k_ps_tile<IMP3D>@8 -- the tests' proof that the override reached kernel_plan)
+        if (s->kplan.grid_override)
             std::snprintf(name, (size_t)name_cap, "%s@%d", bulk_kernel_name(S), s->grid);
         else std::snprintf(name, (size_t)name_cap, "%s", bulk_kernel_name(S));
     }

@@ -267,16 +267,8 @@ hipError_t launch_col_seed_init(const DevState& S, hipStream_t st) {
 WaveArgs make_wave_args(const DevState& S, uint32_t round) {
     const int cur = round & 1;
     WaveArgs a;
-    a.swc = S.sw[cur];
-    a.swn = S.sw[cur ^ 1];
     a.nbc = S.nb[cur];
     a.nbn = S.nb[cur ^ 1];
-    a.rbc = S.rbits[cur];
-    a.rbn = S.rbits[cur ^ 1];
-    a.in_off = S.in_off;
-    a.in_src = S.in_src;
-    a.rtag = S.rtag;
-    a.rmsg = S.rmsg;
     a.c = S.c;
     a.rq_cur = S.rq[round & 1];
     a.rq_next = S.rq[(round + 1) & 1];

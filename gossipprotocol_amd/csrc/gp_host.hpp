@@ -2,7 +2,9 @@
 // gp_xlayout.hip (before round 0), gp_exchange.hip (one round across ranks), gp_api.hip (C ABI,
 // gp_step batch loop) and, for the error slot and device check, gp_ensemble_api.hip.  Hidden
 // symbols: not the library's surface.  What a run over several ranks allocates and addresses is
-// decided by gp_plan.hpp; these units carry it out.
+// decided by gp_plan.hpp, which round kernel it gets by gp_kernel_plan.hpp; these units carry it
+// out.  The experiments build's GP_* overrides are read once, at create, into gp_sim::exp
+// (ExpOverrides; read_overrides, gp_setup.hip).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -13,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -28,19 +31,6 @@
 #include "gp_full.hpp"
 #include "gp_fullbin.hpp"
 
-namespace {
-// The experiments build (-DGP_EXPERIMENTS, libgossip_hip_exp.so) reads the GP_* environment
-// overrides the kernel-variant tests use; the product library reads none (nullptr: every
-// override below folds away, its name included -- tests/test_abi.py checks the strings).
-inline const char* exp_env(const char* name) {
-#ifdef GP_EXPERIMENTS
-    return std::getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
-}  // namespace
 #include "gp_xchg.hpp"
 
 using namespace gp;
@@ -72,7 +62,22 @@ int check_device(int device);
 constexpr int64_t BATCH = 1024;  // rounds queued per host synchronisation (<= HIST)
 static_assert(BATCH <= HIST, "alert ring must cover a batch");
 
-enum Mode { MODE_SINGLE = 0, MODE_VIRTUAL = 1, MODE_RCCL = 2 };
+// The GP_* environment overrides of the experiments build (-DGP_EXPERIMENTS,
+// libgossip_hip_exp.so), which the kernel-variant tests use, as they stood when the handle was
+// created; the product library reads none, so there every field is empty.  An empty field: not set.
+struct ExpOverrides {
+    KernelOverrides kernel;                        // what the kernel plan takes (gp_kernel_plan.hpp)
+    std::optional<uint32_t> fb_cap1, fb_cap2;      // GP_FB_CAP1 / GP_FB_CAP2
+    std::optional<bool> fb_fused;                  // GP_FB_FUSED
+    std::optional<bool> rq8;                       // GP_RQ8
+    std::optional<uint32_t> halo_cap;              // GP_HALO_CAP
+    std::optional<uint32_t> xcap;                  // GP_XCAP
+    std::optional<bool> no_pack;                   // GP_NO_PACK
+    std::optional<uint32_t> ind4_wide;             // GP_IND4_WIDE
+    std::optional<bool> force_rccl;                // GP_FORCE_RCCL
+    bool check_close = false;                      // GP_CHECK_CLOSE (set to anything)
+};
+ExpOverrides read_overrides();  // gp_setup.hip
 
 // One inter-rank transfer of a slab: `bytes` at `ptr`, sent to or received from rank `peer`
 // (build_transfers / run_transfers, gp_exchange.hip).
@@ -125,8 +130,10 @@ struct gp_sim {
     gp_config cfg{};
     int device = 0;
     hipStream_t stream = nullptr;
-    int grid = 1;
-    int cus = 1;  // compute units of the device
+    ExpOverrides exp;  // the experiments build's overrides, read at create
+    KernelPlan kplan;  // kernel variant, walk, grid, regions (gp_kernel_plan.hpp)
+    int grid = 1;      // kplan.grid
+    int cus = 1;       // compute units of the device
     int64_t P = 0, T = 0, g = 0;
     int mode = MODE_SINGLE;
     int world = 1, rank = 0;  // ranks sharing the population; this process's rank (RCCL)
@@ -154,7 +161,6 @@ struct gp_sim {
     std::vector<uint32_t> list_nw;
     hipStream_t xstream = nullptr;
     hipEvent_t ev_send[XMAXH] = {}, ev_xfer[XMAXH] = {};
-    BlockPlan bplan{};  // KERNEL_BLOCK
     // gp_summary_take (gp_summary.hip): partial records and gather buffer, allocated at the first call
     void* sum_scratch = nullptr;
     size_t sum_scratch_bytes = 0;
@@ -199,16 +205,6 @@ struct Scratch {
 // Imp3D gossip on the column kernel: random-edge deliveries are counted by their
 // senders (rq) and cross ranks as counts; no bitmap, in-edge tags or slots.
 inline bool col_gossip_counts(const DevState& S) { return S.topo == IMP3D && S.alg == GOSSIP && S.kernel == KERNEL_COL; }
-
-// Exchange regions of this run's slabs (gp_plan.hpp).  GP_XREGIONS=8 (experiments): the eight
-// regions of two ranks with large slabs at any slab size and world, Imp3D push-sum only; any
-// other value is ignored.
-inline int exchange_regions(const gp_sim* s) {
-    const bool push = s->cfg.algorithm == GP_PUSHSUM, imp3d = s->cfg.topology == GP_IMP3D;
-    if (const char* e = exp_env("GP_XREGIONS"))
-        if (push && imp3d && s->world > 1 && std::atoi(e) == 8) return 8;
-    return exchange_regions(push, imp3d, s->world, s->bounds);
-}
 
 // gp_setup.hip
 int create_common(const gp_config* cfg, int mode, int world, int rank, const uint8_t* uid, gp_sim** out);

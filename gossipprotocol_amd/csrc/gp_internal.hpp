@@ -12,6 +12,7 @@
 #include "gp_block_plan.hpp"
 #pragma GCC visibility push(hidden)  // the plan's inline functions are no part of the library's surface
 #include "gp_plan.hpp"
+#include "gp_kernel_plan.hpp"  // KernelVariant, BULK_THREADS
 #pragma GCC visibility pop
 #include "gp_device.hpp"
 
@@ -19,7 +20,6 @@ namespace gp {
 
 constexpr int HIST = 4096;            // per-round alert ring (host syncs at least every HIST rounds)
 constexpr uint32_t INJ_CHUNK = 65536; // injector live-list chunk (ids); 2048 bitmap words
-constexpr int BULK_THREADS = 256;
 
 // The immediate of `s_waitcnt vmcnt(n)` with the other counters left alone (gfx9 encoding:
 // vmcnt bits 3:0 and 15:14, expcnt 6:4 = 7, lgkmcnt 11:8 = 15), for __builtin_amdgcn_s_waitcnt.
@@ -311,8 +311,6 @@ struct RoundArgs {
     uint32_t* tq_next;   // walk 3: the next round's counters, zeroed by block 0 this round
 };
 
-enum KernelVariant : int { KERNEL_TILE = 1, KERNEL_COL = 2, KERNEL_BLOCK = 3 };
-
 // ---- LDS-resident push-sum on a small 3D lattice (gp_block.hip): one cooperative launch
 // per batch of rounds (BlockPlan and block_plan: gp_block_plan.hpp)
 size_t block_face_bytes(const BlockPlan& p);
@@ -327,16 +325,8 @@ hipError_t launch_round_block(const struct DevState& S, const BlockPlan& p, uint
 
 // Arguments of the column-march gossip kernels (gp_col.hip).
 struct WaveArgs {
-    const double2* swc;
-    double2* swn;
     const uint8_t* nbc;
     uint8_t* nbn;
-    const uint64_t* rbc;
-    uint64_t* rbn;
-    const uint32_t* in_off;
-    const uint32_t* in_src;
-    const uint32_t* rtag;
-    const double2* rmsg;
     int32_t* c;
     uint32_t* rq_cur;        // Imp3D gossip: this round's random-edge deliveries per local node (read, then zeroed)
     uint32_t* rq_next;       // next round's, counted by local senders with atomics (remote ones: k_unpack)

@@ -393,8 +393,8 @@ hipError_t launch_bulk(const DevState& S, uint32_t round, int grid, hipStream_t 
 }
 
 const char* bulk_kernel_name(const DevState& S) {
-    static const char* ps[2][4] = {{"k_ps_tile<LINE>", "k_fb_send+split+fold", "k_ps_tile<GRID3D>", "k_ps_tile<IMP3D>"},
-                                   {"k_ps_tile<LINE>", "k_fb_send+split+fold", "k_ps_col<GRID3D>", "k_ps_col<IMP3D>"}};
+    // (push-sum has no column kernel: plan_variant, gp_kernel_plan.hpp)
+    static const char* ps[4] = {"k_ps_tile<LINE>", "k_fb_send+split+fold", "k_ps_tile<GRID3D>", "k_ps_tile<IMP3D>"};
     static const char* go[2][4] = {{"k_gossip_tile<LINE>", "k_full_gossip_send+recv", "k_gossip_tile<GRID3D>",
                                     "k_gossip_tile<IMP3D>"},
                                    {"k_gossip_tile<LINE>", "k_full_gossip_send+recv", "k_gossip_col<GRID3D>",
@@ -405,7 +405,7 @@ const char* bulk_kernel_name(const DevState& S) {
     // the 1024-thread size class (gp_ps_tile_wide.hip): line and 3D push-sum
     if (v == 0 && S.tile_wide && S.alg == PUSHSUM && (S.topo == LINE || S.topo == GRID3D))
         return S.topo == LINE ? "wide::k_ps_tile<LINE>" : "wide::k_ps_tile<GRID3D>";
-    return S.alg == PUSHSUM ? ps[v][S.topo] : go[v][S.topo];
+    return S.alg == PUSHSUM ? ps[S.topo] : go[v][S.topo];
 }
 
 // Experiments build, GP_CHECK_CLOSE=1 (tests): the alert bookkeeping recounted

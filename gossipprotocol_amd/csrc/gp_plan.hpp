@@ -5,7 +5,9 @@
 // gp_exchange.hip).  Host-only and free of HIP headers, like gp_block_plan.hpp, so that a plain
 // C++ program can evaluate it (tests/helpers/plan_check.cpp): tests/test_plan.py compares it with
 // the restatements in tests/multirank_emu.py that the GPU edge tests derive their cases from.
-// The experiments build's GP_* overrides are applied to the plan's results by the host units.
+// Which round kernel, walk and grid the run gets is decided beside it, in gp_kernel_plan.hpp.
+// The experiments build's GP_* overrides (ExpOverrides, gp_host.hpp) are applied to this plan's
+// results by the host units.
 #pragma once
 
 #include <stddef.h>
@@ -173,7 +175,7 @@ inline int exchange_regions(bool push, bool imp3d, int W, const std::vector<uint
 
 // Imp3D push-sum across ranks with NH exchange regions: may the round kernel run region by
 // region (DevState::rregions = NH)?  `on`: every slab holds at least RREG_MIN_NODES nodes (small
-// slabs move little and keep one launch per round; see round_regions, gp_setup.hip).
+// slabs move little and keep one launch per round; see round_regions, gp_kernel_plan.hpp).
 inline bool round_regions_on(int W, const std::vector<uint32_t>& bounds) {
     for (int w = 0; w < W; ++w)
         if (bounds[w + 1] - bounds[w] < RREG_MIN_NODES) return false;

@@ -20,7 +20,7 @@ uint32_t bits_for(uint64_t maxval) {
 int build_lists(gp_sim* s, const uint32_t* rnd_all, uint32_t* kk, const uint32_t* src,
                 const std::vector<uint32_t>& edge0) {
     const int W = s->world;
-    const int NH = s->xhalves = exchange_regions(s);
+    const int NH = s->xhalves = s->kplan.xregions;
     s->list_nw.assign((size_t)W * NH * W, 0);
     std::vector<std::vector<uint32_t>> gw_all(W);
     std::vector<std::vector<uint8_t>> lwt_all(W);
@@ -248,8 +248,7 @@ int build_imp3d(gp_sim* s) {
             HIP_TRY(hipMemcpyAsync(S.in_src, src_sorted + edge0[r], sizeof(uint32_t) * ne,
                                    hipMemcpyDeviceToDevice, s->stream));
         S.in_srcd = nullptr;
-        bool pack = true;
-        if (const char* np = exp_env("GP_NO_PACK")) pack = np[0] != '1';  // force the unpacked (P > 2^30) path
+        const bool pack = !s->exp.no_pack.value_or(false);  // (GP_NO_PACK=1: force the unpacked (P > 2^30) path)
         if (S.alg == PUSHSUM && S.kernel == KERNEL_TILE && s->P <= (1ll << 30) && s->g >= 2 && pack) {
             if ((rc = dev_alloc_t(s, &S.in_srcd, (size_t)ne + 4))) return rc;
             if (ne) HIP_TRY(launch_pack_src_deg(S.in_src, S.in_srcd, ne, S.G, s->grid, s->stream));
@@ -257,8 +256,7 @@ int build_imp3d(gp_sim* s) {
         S.ind4 = nullptr;
         if (S.alg == PUSHSUM && S.kernel == KERNEL_TILE) {
             if ((rc = dev_alloc_t(s, &S.ind4, ind4_bytes_for(S.lo, S.nloc)))) return rc;
-            uint32_t wide_at = 15;  // in-degree >= 15: the tile reads in_off (gp_ps_tile.hip)
-            if (const char* e = exp_env("GP_IND4_WIDE")) wide_at = (uint32_t)std::max(1, std::atoi(e));
+            const uint32_t wide_at = s->exp.ind4_wide.value_or(15);  // in-degree >= 15: the tile reads in_off (gp_ps_tile.hip; GP_IND4_WIDE)
             HIP_TRY(launch_pack_ind4(S, wide_at, s->grid, s->stream));
         }
         if (W > 1 && !col_gossip_counts(S)) {  // (the gossip column kernel's bitmaps: build_bits)

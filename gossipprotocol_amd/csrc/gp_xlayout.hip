@@ -18,7 +18,7 @@ int setup_exchange(gp_sim* s) {
         for (Slab& sl : s->slab) sl.overflow = &sl.S.ctl->overflow;
         return GP_OK;
     }
-    const int NH = exchange_regions(s);
+    const int NH = s->kplan.xregions;
     s->xhalves = NH;
     std::vector<uint32_t> caps((size_t)NH * W * W, 0);  // caps[(h * W + a) * W + b]: a -> b, region h
     Scratch tmp_mem;
@@ -81,10 +81,8 @@ int setup_exchange(gp_sim* s) {
             }
         }
     }
-    if (const char* e = exp_env("GP_XCAP")) {  // tests: force tiny buffers (overflow handling)
-        const uint32_t cap = (uint32_t)std::max(1, std::atoi(e));
-        for (auto& c : caps) c = std::min(c, cap);
-    }
+    if (s->exp.xcap)  // (GP_XCAP) tests: force tiny buffers (overflow handling)
+        for (auto& c : caps) c = std::min(c, *s->exp.xcap);
     if (s->mode == MODE_RCCL && !full) {
         // every rank learns the capacities of the buffers it will receive (per region)
         uint32_t* d = nullptr;

@@ -25,12 +25,18 @@
 //       -> ok send recv own hdr_in xr_stride xnv ; cap_out ; cap_in ; soff ; sbytes ; roff ;
 //          rbytes ; ooff ; lhdr ; lval ; rhdr ; rval ; vbase
 //   walk lo nloc g2 wx NR                  -> ok ; woff[h][0..8]... ; list
+//   kernel_plan topo alg P g W mode  cus col_blocks_per_cu res4 res_wide block_resident
+//               kernel xsegs walk wx wide rregions xregions fuse stage_cap no_full grid
+//       (gp_kernel_plan.hpp; the overrides as parsed, "-" for one not set, grid as its text; the
+//       facts are what the device queries would answer, and gather_kernel_facts picks from them)
+//       -> bad_grid grid_max ; kernel col_xsegs walk wx wide grid rregions fuse_finalize
+//          stage_cap no_full xregions grid_override ; bplan ; queries made (block, col, res4, wide)
 #include <cstdio>
 #include <iostream>
 #include <sstream>
 #include <string>
 
-#include "../../gossipprotocol_amd/csrc/gp_plan.hpp"
+#include "../../gossipprotocol_amd/csrc/gp_kernel_plan.hpp"
 
 using namespace gp;
 
@@ -219,6 +225,45 @@ int main() {
             for (int h = 0; h < NR && h < RREG_MAX; ++h)
                 for (int c = 0; c <= 8; ++c) std::printf(" %u", woff[h][c]);
             put(list);
+        } else if (q == "kernel_plan") {
+            RunShape r;
+            long long P;
+            KernelFacts have;
+            int block = 0;
+            in >> r.topology >> r.algorithm >> P >> r.g >> r.world >> r.mode >> have.cus >> have.col_blocks_per_cu >>
+                have.res4 >> have.res_wide >> block;
+            have.block_resident = block != 0;
+            uint32_t halo = 0;
+            slab_bounds(P, r.g, r.world,
+                        r.topology == RunShape::Full ? SlabCut::Full : r.topology == RunShape::Line ? SlabCut::Line : SlabCut::Planes,
+                        r.bounds, halo);
+            auto opt = [&](auto& field) {
+                std::string tok;
+                in >> tok;
+                if (tok != "-") field = (typename std::decay_t<decltype(field)>::value_type)std::stoll(tok);
+            };
+            KernelOverrides ov;
+            opt(ov.kernel), opt(ov.xsegs), opt(ov.walk), opt(ov.wx), opt(ov.wide), opt(ov.rregions), opt(ov.xregions);
+            opt(ov.fuse), opt(ov.stage_cap), opt(ov.no_full);
+            std::string grid;
+            in >> grid;
+            if (grid != "-") ov.grid = grid;
+            struct Device {  // answers from `have`, counting what is asked
+                const KernelFacts& have;
+                int asked[4] = {};
+                int cus() { return have.cus; }
+                bool block_resident(const BlockPlan&, int) { return ++asked[0], have.block_resident; }
+                int col_blocks_per_cu() { return ++asked[1], have.col_blocks_per_cu; }
+                int res4() { return ++asked[2], have.res4; }
+                int res_wide() { return ++asked[3], have.res_wide; }
+            } dev{have};
+            const KernelFacts f = gather_kernel_facts(r, ov, dev);
+            KernelPlanError err;
+            const KernelPlan p = kernel_plan(r, f, ov, err);
+            std::printf(" %d %d ; %d %u %u %u %u %d %u %u %u %u %d %d ; %u %u %u %u %u %u ; %d %d %d %d", err.bad_grid ? 1 : 0,
+                        err.grid_max, p.kernel, p.col_xsegs, p.walk, p.wx, p.wide, p.grid, p.rregions, p.fuse_finalize,
+                        p.stage_cap, p.no_full, p.xregions, p.grid_override ? 1 : 0, p.bplan.nbx, p.bplan.nby, p.bplan.nbz,
+                        p.bplan.vmax, p.bplan.fmax, p.bplan.lds, dev.asked[0], dev.asked[1], dev.asked[2], dev.asked[3]);
         } else {
             std::printf(" ?");
         }

@@ -344,3 +344,69 @@ def test_walk_list_covers_the_slab_once(plan, g, W, NR, wx):
             assert sorted(tiles[woff[9 * h]:woff[9 * h + 8]]) == list(range(tb[h], tb[h + 1]))
     (ok, *_), = plan([("walk", 5, 4096, 4096, 16, 1)])
     assert ok == [0]  # not plane-aligned
+
+
+# ---- the kernel plan (gp_kernel_plan.hpp) against the decisions recorded before the rules moved there
+KERNELS = {"tile": 1, "col": 2, "block": 3}  # KernelVariant; any other text: 0
+# (name in the golden file, how read_overrides (gp_setup.hip) parses its text)
+OVERRIDES = [("GP_KERNEL", lambda t: KERNELS.get(t, 0)), ("GP_XSEGS", lambda t: max(1, int(t))), ("GP_WALK", int),
+             ("GP_WX", lambda t: max(1, int(t))), ("GP_WIDE", lambda t: int(t[:1] == "1")), ("GP_RREGIONS", int),
+             ("GP_XREGIONS", int), ("GP_FUSE", lambda t: ord(t[0]) - ord("0")), ("GP_STAGE_CAP", lambda t: max(0, int(t))),
+             ("GP_NO_FULLTILE", lambda t: int(t[:1] == "1")), ("GP_GRID", str)]
+PLAN_FIELDS = ("kernel", "col_xsegs", "walk", "wx", "wide", "grid", "rregions", "fuse_finalize", "stage_cap", "no_full",
+               "xregions", "grid_override")
+
+
+@pytest.fixture(scope="module")
+def kernel_plan_golden():
+    """The cases of tests/golden/kernel_plan.json as (shape, facts, overrides, decision)."""
+    import json
+    with open(os.path.join(HERE, "golden", "kernel_plan.json")) as f:
+        return [tuple(c) for c in json.load(f)["cases"]]
+
+
+def test_kernel_plan_replays_the_recorded_decisions(plan, kernel_plan_golden):
+    """Every case of tests/golden/kernel_plan.json (recorded from choose_kernel / round_regions as they
+    stood in gp_setup.hip, see the file's header): kernel_plan gives the same plan, field for field, or
+    the same GP_GRID error; and gather_kernel_facts asks the device exactly what was asked then."""
+    cases = kernel_plan_golden
+    assert all(set(ov) <= {name for name, _ in OVERRIDES} for _, _, ov, _ in cases)
+    q = [("kernel_plan", *shape, *facts, *[parse(ov[name]) if name in ov else "-" for name, parse in OVERRIDES])
+         for shape, facts, ov, _ in cases]
+    bad = []
+    for (shape, facts, ov, want), (err, fields, bplan, asked) in zip(cases, plan(q)):
+        got = "GP_GRID=%s: not a grid of 1..%d blocks" % (ov["GP_GRID"], err[1]) if err[0] else fields + bplan + asked
+        if got != want:
+            bad.append((shape, facts, ov, want, got))
+    assert not bad, "%d of %d cases differ, the first: %r" % (len(bad), len(cases), bad[0])
+
+
+def test_kernel_plan_golden_holds_the_cases_where_a_rule_flips(kernel_plan_golden):
+    """The sweep crosses every threshold of the rules (both sides present among the recorded decisions)."""
+    ok = [(s, f, ov, dict(zip(PLAN_FIELDS, w))) for s, f, ov, w in kernel_plan_golden if not isinstance(w, str)]
+
+    def seen(pred):
+        return {key for c in ok for key in [pred(*c)] if key is not None}
+    # gossip on a 3D / Imp3D lattice at g = 199 / 200: tile / column
+    assert seen(lambda s, f, ov, w: (s[0], s[3], w["kernel"]) if s[1] == 0 and s[3] in (199, 200) and not ov else None) == \
+        {(2, 199, 1), (2, 200, 2), (3, 199, 1), (3, 200, 2)}
+    # g / world = 63 / 64: walk 0 / walks 2 (gossip) and 3 (push-sum)
+    assert seen(lambda s, f, ov, w: (s[3] // s[4], s[1], w["walk"]) if s[0] == 3 and s[3] // s[4] in (63, 64) and not ov
+                and f[2] >= 8 else None) == {(63, 0, 0), (63, 1, 0), (64, 0, 2), (64, 1, 3)}
+    # walk 3 with 7 / 8 resident blocks: back to walk 2 (one CU: the 64-per-CU cap) / the resident grid
+    assert seen(lambda s, f, ov, w: (f[2], w["walk"], w["grid"]) if s[:2] == [3, 1] and s[3] // s[4] == 64 and f[2] in (7, 8)
+                and not ov else None) == {(7, 2, 64), (8, 3, 8)}
+    # the wide class up to two tiles per resident block (line push-sum, 256 CUs: 2560 tiles)
+    assert seen(lambda s, f, ov, w: (-(-s[2] // 1024) + 1, w["wide"]) if s[:2] == [0, 1] and s[4] == 1 and f[2] == 1280
+                and s[2] > 10**6 and not ov else None) == {(2560, 1), (2561, 0)}
+    # a 3D push-sum lattice with / without a resident box grid
+    assert seen(lambda s, f, ov, w: (f[4], w["kernel"]) if s[:2] == [2, 1] and s[3:5] == [100, 1] and f[0] == 256 and not ov
+                else None) == {(0, 1), (1, 3)}
+    # Imp3D push-sum at W = 2, slabs below / from RREG_MIN_NODES on: one launch per round / eight regions
+    assert seen(lambda s, f, ov, w: (s[3], w["rregions"]) if s[:2] == [3, 1] and s[3] in (322, 323) and s[4] == 2 and not ov
+                else None) == {(322, 1), (323, 8)}
+    # a GP_GRID that region rounds ignore still marks the name
+    assert seen(lambda s, f, ov, w: (w["grid"] == 12, w["grid_override"]) if w["rregions"] > 1 and ov.get("GP_GRID") == "12"
+                else None) == {(False, 1)}
+    errors = {ov["GP_GRID"] for _, _, ov, w in kernel_plan_golden if isinstance(w, str)}
+    assert {"abc", "0", "-8", "8x", "99999999999999999999", "41"} <= errors
