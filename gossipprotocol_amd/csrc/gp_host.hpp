@@ -74,6 +74,7 @@ struct ExpOverrides {
     std::optional<uint32_t> xcap;                  // GP_XCAP
     std::optional<bool> no_pack;                   // GP_NO_PACK
     std::optional<uint32_t> ind4_wide;             // GP_IND4_WIDE
+    std::optional<bool> slot_shadow;               // GP_SLOT_SHADOW (k_ps_tile; 0: the ordering before DESIGN.md 5.1.0b)
     std::optional<bool> force_rccl;                // GP_FORCE_RCCL
     bool check_close = false;                      // GP_CHECK_CLOSE (set to anything)
 };

@@ -247,6 +247,7 @@ struct DevState {
     uint32_t tile_stage_cap;  // RoundArgs::stage_cap (experiments build only; default: no limit)
 #ifdef GP_EXPERIMENTS
     uint32_t tile_no_full;    // RoundArgs::no_full
+    uint32_t tile_slot_shadow;  // RoundArgs::slot_shadow
 #endif
     uint32_t fuse_finalize;   // the round kernel closes its own round (single rank push-sum)
     BlockPlan bplan;          // KERNEL_BLOCK (gp_block.hip): boxes, face buffer, barrier scratch
@@ -303,6 +304,7 @@ struct RoundArgs {
                          // take the unstaged path (tests force it)
 #ifdef GP_EXPERIMENTS
     uint32_t no_full;    // k_ps_tile: every tile through the general (!FULL) tile body (GP_NO_FULLTILE=1)
+    uint32_t slot_shadow;  // k_ps_tile: 0 = draw at the tile's end, slots decided at their start (GP_SLOT_SHADOW=0)
 #endif
     uint32_t fuse;       // k_ps_tile: the last block closes the round (no k_finalize launch)
     const uint32_t* wt;  // walk 3: tile list (DevState::wtiles), XCD c's items at [wo[c], wo[c + 1])

@@ -15,7 +15,7 @@
 //      from the sender's Philox draw (every node active) or from a ballot-packed
 //      bitmap (activation phase), then gather;
 //   3. fold in canonical order (own half, lattice slots, random edges by
-//      ascending sender), ratio test, next-round Philox draw; node bytes leave
+//      ascending sender), ratio test (the next-round Philox draw runs under the slot's loads); node bytes leave
 //      through LDS as 32-bit words, random-edge bits as one 64-bit ballot per
 //      wave.
 // Built with -ffp-contract=off: the fold must round exactly like the oracle.
@@ -41,7 +41,10 @@ namespace wide {
 //    XCDs' queues (12.85-12.87 -> 12.75-12.81 ms/round; W = 8 slab 1.714 -> 1.699 ms,
 //    profiles/r04/walk_steal.txt);
 //  * the j +- 1 messages from the neighbour lanes' registers by DPP, one node slot's loads
-//    in flight at a time (two spilled), non-temporal staging loads and state stores.
+//    in flight at a time (two spilled), non-temporal staging loads and state stores;
+//  * between a node slot's load issue and its wait: the node's next-round direction draw and
+//    the next slot's sender tests, neither of which needs what the loads return (P = 1e9,
+//    same box, alternated: 11.74-11.99 -> 11.49-11.64 ms/round, profiles/r08/slot_shadow/).
 constexpr int PRIO = 1;  // the raised wave priority
 
 namespace {
@@ -102,8 +105,10 @@ struct TileLdsP {
 //      direction (no sender: the zero sentinel), the canonical fold (own half,
 //      lattice slots in slot order, random edges by ascending sender), the ratio
 //      test (Program.fs:114-123);
-//   4. next-round directions of the thread's NPT nodes as one Philox batch;
-//      node bytes out as words, random-edge bits as one ballot per wave.
+//      Under the slot's loads (nothing here needs what they return): the node's next-round
+//      direction, drawn unconditionally and kept only if the node is active after the fold,
+//      and the next slot's sender tests;
+//   4. node bytes out as words, random-edge bits as one ballot per wave.
 template <int TOPO, bool REMOTE>
 __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLdsP<REMOTE>& L, uint32_t* snd,
                                          bool all_active, uint32_t& alerts, uint32_t& newly, bool& tiny) {
@@ -363,24 +368,32 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
         }
         // (s, w) across every wave's ends, slot k: node T + k*TPB + 64 wave - 1 and + 64
         // (clamped into the node arrays; used only where that neighbour sent)
-        if (lane < 2u * NPT) {
-            // (the lane opaque: its part of the index is then computed here, by 8 lanes per tile, not
-            // kept in a register pair across the tile loop)
-            uint32_t zl = lane;
-            asm volatile("" : "+v"(zl));
-            int64_t jn = (int64_t)T + (int64_t)((zl >> 1) * TPB + wv * 64u) + ((zl & 1u) ? 64 : -1);
-            if (jn < (int64_t)a.ext_lo) jn = a.ext_lo;
-            if (jn > (int64_t)a.ext_hi) jn = a.ext_hi;
-            __builtin_amdgcn_global_load_lds((gvoid_t*)(swc + jn), (lvoid_t*)&L.zb[wv][0][0], 16, 0, 0);
+        {
+            // (the thread index opaque: the lane's and the wave's parts of the index and the wave's LDS
+            // address are then computed here, per tile, not kept in registers across the tile loop,
+            // where they spilled)
+            uint32_t zt = threadIdx.x;
+            asm volatile("" : "+v"(zt));
+            const uint32_t zl = zt & 63u, zw = zt >> 6;
+            if (zl < 2u * NPT) {
+                int64_t jn = (int64_t)T + (int64_t)((zl >> 1) * TPB + zw * 64u) + ((zl & 1u) ? 64 : -1);
+                if (jn < (int64_t)a.ext_lo) jn = a.ext_lo;
+                if (jn > (int64_t)a.ext_hi) jn = a.ext_hi;
+                __builtin_amdgcn_global_load_lds((gvoid_t*)(swc + jn), (lvoid_t*)&L.zb[zw][0][0], 16, 0, 0);
+            }
         }
         // the tile's in-degrees, a nibble per node (512 bytes; the slab's arrays
         // cover whole tiles, ids outside the slab are 0)
         if (TOPO == IMP3D) {
-            // (the tile's base opaque: otherwise a.ind4 + the thread's offset is kept as a 64-bit
-            // address across the tile loop, and spilled)
+            // (the tile's base and the thread index opaque: otherwise a.ind4 + the thread's offset, or
+            // the offset, is kept as a 64-bit value across the tile loop, and spilled.  dma_copy's
+            // one pass written out: 16 bytes per lane of the first TILE / 32 threads)
             const uint8_t* ip = a.ind4 + T / 2;
             asm volatile("" : "+s"(ip));
-            dma_copy<DMA_ONCE>(L.ind, reinterpret_cast<const char*>(ip), TILE / 2);
+            uint32_t nt = threadIdx.x;
+            asm volatile("" : "+v"(nt));
+            if (nt < (uint32_t)(TILE / 32))
+                __builtin_amdgcn_global_load_lds((gvoid_t*)(ip + nt * 16u), (lvoid_t*)L.ind, 16, 0, DMA_ONCE);
         }
         if (dyn && threadIdx.x == 0) L.qn[it & 1] = claim;
         __builtin_amdgcn_s_setprio(0);
@@ -440,16 +453,22 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
 #ifdef GP_EXPERIMENTS
         if (a.no_full) full = false;  // GP_NO_FULLTILE=1: every tile through the general body (A/B, parity tests)
 #endif
-        auto tile_body = [&](auto full_c) {
+        // SHADOW: a slot's work that needs nothing its loads return -- the node's next-round
+        // direction draw, and deciding the next slot -- runs between the loads' issue and their
+        // wait.
+        auto tile_body = [&](auto full_c, auto shadow_c) {
         constexpr bool FULL = decltype(full_c)::value;
+        constexpr bool SHADOW = decltype(shadow_c)::value;
         // the thread index is opaque to each body: what a body derives from it (lane tests, byte
         // offsets, per-thread address parts) is computed once per tile, not hoisted out of the tile
         // loop into registers that stay live across the in-edge pass (two bodies' worth spilled)
         uint32_t tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const uint32_t lane = tid & 63u, wv = tid >> 6;
-        // per node, 16 bits (two nodes per word): bits 0-5 lattice mask, bit 6 draw a
-        // next-round direction, bits 7-10 the node byte's flag bits 3-6
+        // per node, 16 bits (two nodes per word).  SHADOW: the next-round node byte -- bits 0-2 the
+        // candidate direction parked before the fold, raised to DIR_NONE after it if the node does
+        // not send, bits 3-6 the flags.  Otherwise: bits 0-5 lattice mask, bit 6 draw a next-round
+        // direction, bits 7-10 the node byte's flag bits 3-6
         uint32_t pend[(NPT + 1) / 2];
 #pragma unroll
         for (int k = 0; k < (NPT + 1) / 2; ++k) pend[k] = 0u;
@@ -470,108 +489,124 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
             // lattice directions gathered from HBM / L2; the j +- 1 ones (z +- 1, or both
             // line neighbours) are the neighbour lanes' own (s, w)
             constexpr uint32_t NDG = TOPO == LINE ? 0u : 4u;
-            constexpr int NG = 1;  // node slots per group in flight (2 at 5 waves/SIMD spilled 49 VGPRs)
-#pragma unroll
-            for (int k0 = 0; k0 < NPT; k0 += NG) {
-                __builtin_amdgcn_s_setprio(PRIO);
-                // phase A: node byte, present mask, lattice senders (from the staged
-                // direction bytes), one gather per direction -- a direction without a
-                // sender reads the zero sentinel swc[ext_hi] (adding +0.0 is exact)
-                // in-edge ranges of the group's nodes (all lanes take part in the ballots)
-                uint32_t epre[NG], edeg[NG];
-#pragma unroll
-                for (int h = 0; h < NG; ++h) {
-                    epre[h] = edeg[h] = 0u;
-                    if (TOPO == IMP3D) {
-                        const int k = k0 + h;
-                        const uint32_t jl = k * TPB + tid;
-                        const uint32_t d = (lds_byte(L.ind, jl >> 1) >> ((jl & 1u) * 4u)) & 15u;
-                        uint32_t ex = mbcnt64(__ballot(d & 1u)) + 2u * mbcnt64(__ballot(d & 2u));
-                        if (__ballot(d >= 4u)) ex += 4u * mbcnt64(__ballot(d & 4u)) + 8u * mbcnt64(__ballot(d & 8u));
-                        const int wvu = __builtin_amdgcn_readfirstlane((int)wv);
-                        epre[h] = (uint32_t)__builtin_amdgcn_readlane((int)cinc, 16 * k + 4 * wvu) + ex;
-                        edeg[h] = d;
+            // A slot in two parts.  decide(k): what the staged LDS bytes and the wave coordinates
+            // settle -- the node's in-edge range (all lanes take part in the ballots), its byte,
+            // present mask and lattice senders, packed as byte | mask << 8 | from << 14 |
+            // in-degree << 20 (one register) -- and the coordinate step to slot k.  Then the issue:
+            // own (s, w) and one gather per direction, whose addresses `from` picks.
+            auto decide = [&](const int k, uint32_t& gst, uint32_t& epre) {
+                epre = 0u;
+                uint32_t edeg = 0u;
+                if (TOPO == IMP3D) {
+                    const uint32_t jl = k * TPB + tid;
+                    const uint32_t d = (lds_byte(L.ind, jl >> 1) >> ((jl & 1u) * 4u)) & 15u;
+                    uint32_t ex = mbcnt64(__ballot(d & 1u)) + 2u * mbcnt64(__ballot(d & 2u));
+                    if (__ballot(d >= 4u)) ex += 4u * mbcnt64(__ballot(d & 4u)) + 8u * mbcnt64(__ballot(d & 8u));
+                    const int wvu = __builtin_amdgcn_readfirstlane((int)wv);
+                    epre = (uint32_t)__builtin_amdgcn_readlane((int)cinc, 16 * k + 4 * wvu) + ex;
+                    edeg = d;
+                }
+                const uint32_t j = T + k * TPB + tid;
+                if (TOPO != LINE && k > 0) {
+                    wcz += TPB;
+                    if (wcz >= G.g) {
+                        const uint32_t q = fastdiv(wcz, G.div_g);
+                        wcz -= q * G.g;
+                        wcy += q;
+                        if (wcy >= G.g) {
+                            const uint32_t q2 = fastdiv(wcy, G.div_g);
+                            wcy -= q2 * G.g;
+                            wcx += q2;
+                        }
                     }
                 }
-                // per node: byte | mask << 8 | from << 14 | in-degree << 20 (one register)
-                uint32_t gst[NG];
-                double2 m[NG][NDG > 0 ? NDG : 1];
+                const uint32_t jr = j - b_rows;
+                const uint32_t gbv = lds_byte(L.rows, jr);
+                uint32_t mask;
+                if (TOPO == LINE) {
+                    mask = present_mask<TOPO>(j, G);
+                } else {
+                    const uint32_t gm = G.g - 1u;
+                    const bool interior = wcz >= 1u && wcz + 64u < gm && wcy >= 1u && wcy < gm && wcx >= 1u && wcx < gm;
+                    mask = interior ? 63u : present_mask<TOPO>(j, G);
+                }
+                uint32_t from = 0;
+                if (TOPO == LINE) {
+                    from |= ((mask & 1u) && (lds_byte(L.rows, (mask & 1u) ? jr - 1 : jr) & DIR_MASK) == 1u) ? 1u : 0u;
+                    from |= ((mask & 2u) && (lds_byte(L.rows, (mask & 2u) ? jr + 1 : jr) & DIR_MASK) == 0u) ? 2u : 0u;
+                } else {
+                    // absent neighbours read a harmless in-range byte and are masked out
+                    const uint32_t bxm = lds_byte(L.xm, (mask & 1u) ? j - G.g2 - b_xm : 0u);
+                    const uint32_t bxp = lds_byte(L.xp, (mask & 2u) ? j + G.g2 - b_xp : 0u);
+                    const uint32_t byp = lds_byte(L.rows, (mask & 4u) ? jr + G.g : jr);
+                    const uint32_t bym = lds_byte(L.rows, (mask & 8u) ? jr - G.g : jr);
+                    uint32_t bzp, bzm;
+                    if constexpr (FULL) {
+                        // z +- 1 are lanes +- 1: their direction byte by DPP (every lane is
+                        // active in a full tile); across the wave's ends one LDS byte: lane 63
+                        // reads j + 1, lane 0 j - 1 (index kept >= 0: node 0 has no z - 1), the
+                        // lanes between read j - 1 as well and do not use it
+                        const uint32_t be = lds_byte(L.rows, lane == 63u ? jr + 1u : max(jr, 1u) - 1u);
+                        bzp = (uint32_t)__builtin_amdgcn_mov_dpp((int)gbv, 0x130, 0xF, 0xF, true);
+                        bzm = (uint32_t)__builtin_amdgcn_mov_dpp((int)gbv, 0x138, 0xF, 0xF, true);
+                        if (lane == 63u) bzp = be;
+                        if (lane == 0u) bzm = be;
+                    } else {
+                        bzp = lds_byte(L.rows, (mask & 16u) ? jr + 1 : jr);
+                        bzm = lds_byte(L.rows, (mask & 32u) ? jr - 1 : jr);
+                    }
+                    from =((bxm & DIR_MASK) == 1u ? 1u : 0u) | ((bxp & DIR_MASK) == 0u ? 2u : 0u) |
+                           ((byp & DIR_MASK) == 3u ? 4u : 0u) | ((bym & DIR_MASK) == 2u ? 8u : 0u) |
+                           ((bzp & DIR_MASK) == 5u ? 16u : 0u) | ((bzm & DIR_MASK) == 4u ? 32u : 0u);
+                    from &= mask;
+                }
+                if (!FULL && !(j >= j0 && j < j1)) from = 0u;
+                gst = gbv | (mask << 8) | (from << 14) | (edeg << 20);
+            };
+            // SHADOW: slot k + 1 is decided while slot k's loads are in flight, and only its packed
+            // word and in-edge prefix are carried to its issue; slot 0 is decided here, after the
+            // staging barrier.  One node slot's loads are in flight at a time (two at 5 waves/SIMD
+            // spilled 49 VGPRs).
+            constexpr bool AHEAD = SHADOW;
+            uint32_t gst_n = 0u, epre_n = 0u;
+            if (AHEAD) {
+                __builtin_amdgcn_s_setprio(PRIO);
+                decide(0, gst_n, epre_n);
+            }
 #pragma unroll
-                for (int h = 0; h < NG; ++h) {
-                    const int k = k0 + h;
-                    const uint32_t j = T + k * TPB + tid;
-                    if (TOPO != LINE && k > 0) {
-                        wcz += TPB;
-                        if (wcz >= G.g) {
-                            const uint32_t q = fastdiv(wcz, G.div_g);
-                            wcz -= q * G.g;
-                            wcy += q;
-                            if (wcy >= G.g) {
-                                const uint32_t q2 = fastdiv(wcy, G.div_g);
-                                wcy -= q2 * G.g;
-                                wcx += q2;
-                            }
-                        }
-                    }
-                    const uint32_t jr = j - b_rows;
-                    const uint32_t gbv = lds_byte(L.rows, jr);
-                    uint32_t mask;
-                    if (TOPO == LINE) {
-                        mask = present_mask<TOPO>(j, G);
-                    } else {
-                        const uint32_t gm = G.g - 1u;
-                        const bool interior = wcz >= 1u && wcz + 64u < gm && wcy >= 1u && wcy < gm && wcx >= 1u && wcx < gm;
-                        mask = interior ? 63u : present_mask<TOPO>(j, G);
-                    }
-                    uint32_t from = 0;
-                    if (TOPO == LINE) {
-                        from |= ((mask & 1u) && (lds_byte(L.rows, (mask & 1u) ? jr - 1 : jr) & DIR_MASK) == 1u) ? 1u : 0u;
-                        from |= ((mask & 2u) && (lds_byte(L.rows, (mask & 2u) ? jr + 1 : jr) & DIR_MASK) == 0u) ? 2u : 0u;
-                    } else {
-                        // absent neighbours read a harmless in-range byte and are masked out
-                        const uint32_t bxm = lds_byte(L.xm, (mask & 1u) ? j - G.g2 - b_xm : 0u);
-                        const uint32_t bxp = lds_byte(L.xp, (mask & 2u) ? j + G.g2 - b_xp : 0u);
-                        const uint32_t byp = lds_byte(L.rows, (mask & 4u) ? jr + G.g : jr);
-                        const uint32_t bym = lds_byte(L.rows, (mask & 8u) ? jr - G.g : jr);
-                        uint32_t bzp, bzm;
-                        if constexpr (FULL) {
-                            // z +- 1 are lanes +- 1: their direction byte by DPP (every lane is
-                            // active in a full tile); across the wave's ends one LDS byte: lane 63
-                            // reads j + 1, lane 0 j - 1 (index kept >= 0: node 0 has no z - 1), the
-                            // lanes between read j - 1 as well and do not use it
-                            const uint32_t be = lds_byte(L.rows, lane == 63u ? jr + 1u : max(jr, 1u) - 1u);
-                            bzp = (uint32_t)__builtin_amdgcn_mov_dpp((int)gbv, 0x130, 0xF, 0xF, true);
-                            bzm = (uint32_t)__builtin_amdgcn_mov_dpp((int)gbv, 0x138, 0xF, 0xF, true);
-                            if (lane == 63u) bzp = be;
-                            if (lane == 0u) bzm = be;
-                        } else {
-                            bzp = lds_byte(L.rows, (mask & 16u) ? jr + 1 : jr);
-                            bzm = lds_byte(L.rows, (mask & 32u) ? jr - 1 : jr);
-                        }
-                        from =((bxm & DIR_MASK) == 1u ? 1u : 0u) | ((bxp & DIR_MASK) == 0u ? 2u : 0u) |
-                               ((byp & DIR_MASK) == 3u ? 4u : 0u) | ((bym & DIR_MASK) == 2u ? 8u : 0u) |
-                               ((bzp & DIR_MASK) == 5u ? 16u : 0u) | ((bzm & DIR_MASK) == 4u ? 32u : 0u);
-                        from &= mask;
-                    }
-                    if (!FULL && !(j >= j0 && j < j1)) from = 0u;
-                    gst[h] = gbv | (mask << 8) | (from << 14) | (edeg[h] << 20);
+            for (int k = 0; k < NPT; ++k) {
+                __builtin_amdgcn_s_setprio(PRIO);
+                // phase A: decide (above), then one gather per direction -- a direction without a
+                // sender reads the zero sentinel swc[ext_hi] (adding +0.0 is exact)
+                uint32_t gst, epre;
+                if (AHEAD) {
+                    gst = gst_n;
+                    epre = epre_n;
+                } else {
+                    decide(k, gst, epre);
+                }
+                const uint32_t jl = k * TPB + tid;
+                const uint32_t j = T + jl;
+                double2 m[NDG > 0 ? NDG : 1];
+                {
+                    const uint32_t from = (gst >> 14) & 63u;
                     // unconditional (index clamped into the tile's valid range; invalid lanes'
                     // values are never used): a load under a branch made the compiler wait
                     // for it before issuing the lattice gathers
                     own[k] = swc[FULL ? j : min(max(j, j0), j1 - 1u)];
 #pragma unroll
                     for (uint32_t d = 0; d < NDG; ++d)
-                        m[h][d] = ld_sw(swc + ((from >> d) & 1u ? nbr<TOPO>(j, d, G) : a.ext_hi));
+                        m[d] = ld_sw(swc + ((from >> d) & 1u ? nbr<TOPO>(j, d, G) : a.ext_hi));
                 }
                 __builtin_amdgcn_s_setprio(0);
+                // SHADOW: everything from here to the second barrier needs nothing the slot's loads
+                // return and runs while they are in flight; the scheduler may neither hoist it above
+                // their issue nor sink it below the wait
+                if (SHADOW) __builtin_amdgcn_sched_barrier(0);
                 // phase B: canonical fold (own half, lattice slots in slot order, random
                 // edges by ascending sender; every message contributes the sender's half),
                 // ratio test, next-round state
-#pragma unroll
-                for (int h = 0; h < NG; ++h) {
-                    const int k = k0 + h;
-                    const uint32_t jl = k * TPB + tid;
-                    const uint32_t j = T + jl;
+                {
                     const bool valid = FULL || (j >= j0 && j < j1);
                     // Imp3D, staged tile: the node's window of the used-in-edge bitmap and its first
                     // used in-edge's message, read from LDS while the slot's loads are in flight (the
@@ -580,9 +615,22 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                     uint32_t pwin = 0u, pqb = 0u;
                     if (TOPO == IMP3D && (FULL || (staged && !wide))) {
                         const uint32_t* bw = reinterpret_cast<const uint32_t*>(L.bits);
-                        pqb = epre[h];
-                        const uint32_t nd = gst[h] >> 20;
+                        pqb = epre;
+                        const uint32_t nd = gst >> 20;
                         pwin = __builtin_amdgcn_alignbit(bw[(pqb >> 5) + 1], bw[pqb >> 5], pqb & 31u) & ((1u << nd) - 1u);
+                    }
+                    if (SHADOW) {
+                        // the node's next-round draw depends on its id, the round and its degree alone:
+                        // drawn unconditionally, reduced to the candidate direction and parked in the
+                        // direction bits of the node's half of `pend`; whether the node sends at all
+                        // is known only after the fold
+                        uint32_t x, y;
+                        philox2(j, r + 1, S_PUSHSUM, a.k0, a.k1, x, y);
+                        const uint32_t mask = (gst >> 8) & 63u;
+                        const uint32_t cand = slot_to_dir_fast(mask, uniform_from(x, y, popc6(mask) + (TOPO == IMP3D ? 1u : 0u)));
+                        pend[k >> 1] |= cand << (16 * (k & 1));
+                        if (AHEAD && k + 1 < NPT) decide(k + 1, gst_n, epre_n);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                     // j + 1 / j - 1: the neighbour lane's own (s, w) by DPP (all lanes active
                     // here), across the wave's ends from the values staged in L.zb; a load
@@ -591,7 +639,7 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                     double2 zP = make_double2(0.0, 0.0), zM = zP;
                     {
                         constexpr uint32_t dP = TOPO == LINE ? 1u : 4u, dM = TOPO == LINE ? 0u : 5u;
-                        const uint32_t from = (gst[h] >> 14) & 63u;
+                        const uint32_t from = (gst >> 14) & 63u;
                         zP = dpp_double2<0x130>(own[k]);  // wave_shl:1 -- lane + 1's (s, w)
                         zM = dpp_double2<0x138>(own[k]);  // wave_shr:1 -- lane - 1's (s, w)
                         if (lane == 63u) zP = L.zb[wv][k][1];
@@ -607,7 +655,7 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                     // range with no valid node skips the fold that consumes the loads)
                     __builtin_amdgcn_s_waitcnt(vmcnt_enc(0));
                     if (valid) {
-                        const uint32_t b = gst[h] & 0xFFu, mask = (gst[h] >> 8) & 63u, from = (gst[h] >> 14) & 63u;
+                        const uint32_t b = gst & 0xFFu, mask = (gst >> 8) & 63u, from = (gst >> 14) & 63u;
                         const uint32_t deg = popc6(mask) + (TOPO == IMP3D ? 1u : 0u);
                         bool active = (b & B_ACTIVE) != 0;
                         const double2 sv = own[k];
@@ -632,12 +680,12 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                             fold(zP);
                         } else {
 #pragma unroll
-                            for (uint32_t d = 0; d < NDG; ++d) fold(m[h][d]);
+                            for (uint32_t d = 0; d < NDG; ++d) fold(m[d]);
                             fold(zP);
                             fold(zM);
                         }
                         if (TOPO == IMP3D) {
-                            uint32_t e_b = e_lo + epre[h], e_e = e_b + (gst[h] >> 20);
+                            uint32_t e_b = e_lo + epre, e_e = e_b + (gst >> 20);
                             if (!FULL && wide) {
                                 e_b = a.in_off[j];
                                 e_e = a.in_off[j + 1];
@@ -713,15 +761,20 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                                 active = true;
                             }
                         }
-                        // next-round direction drawn below, one Philox batch for the thread's nodes
-                        pend[k >> 1] |= (mask | (active && deg > 0 ? 64u : 0u) | ((flags >> 3) << 7)) << (16 * (k & 1));
+                        if (SHADOW) {
+                            // the parked candidate stands if the node sends; DIR_NONE (all three bits) otherwise
+                            pend[k >> 1] |= ((active && deg > 0 ? 0u : (uint32_t)DIR_NONE) | (flags & 0x78u)) << (16 * (k & 1));
+                        } else {
+                            // next-round direction drawn below, one Philox batch for the thread's nodes
+                            pend[k >> 1] |= (mask | (active && deg > 0 ? 64u : 0u) | ((flags >> 3) << 7)) << (16 * (k & 1));
+                        }
                         st_stream(swn + j, make_double2(acc_s, acc_w));
                     }
                 }
                 // SNDPF: after the first node slot (the next tile's in-edge range has arrived by
                 // then), its senders by LDS-DMA; this tile's were read in its in-edge pass, and the
                 // tile's closing barrier retires the copy before the next tile reads it
-                if (SNDPF && TOPO == IMP3D && k0 == 0) {
+                if (SNDPF && TOPO == IMP3D && k == 0) {
                     snd_tile = 0xFFFFFFFFu;
                     if (pf_tile != 0xFFFFFFFFu && pf_hi - pf_lo <= cap) {
                         snd_off = dma_stage_words(snd, srcp, pf_lo, pf_hi);
@@ -730,21 +783,29 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
                 }
             }
         }
-        // next-round directions of this thread's nodes: one Philox batch
+        // next-round node bytes of this thread's nodes (SHADOW: as the slots left them; otherwise
+        // the directions are drawn here, one Philox batch)
         {
             uint32_t node[NPT], x[NPT], y[NPT];
 #pragma unroll
             for (int k = 0; k < NPT; ++k) node[k] = T + k * TPB + tid;
-            philox2_batch<NPT>(node, r + 1, S_PUSHSUM, a.k0, a.k1, x, y);
+            if (!SHADOW) philox2_batch<NPT>(node, r + 1, S_PUSHSUM, a.k0, a.k1, x, y);
 #pragma unroll
             for (int k = 0; k < NPT; ++k) {
                 const uint32_t jl = k * TPB + tid;
                 const bool valid = FULL || (node[k] >= j0 && node[k] < j1);
                 const uint32_t pk = pend[k >> 1] >> (16 * (k & 1));
-                const uint32_t mask = pk & 63u;
-                uint32_t dir = DIR_NONE;
-                if (pk & 64u) dir = slot_to_dir_fast(mask, uniform_from(x[k], y[k], popc6(mask) + (TOPO == IMP3D ? 1u : 0u)));
-                if (valid) reinterpret_cast<uint8_t*>(L.out)[jl] = (uint8_t)((((pk >> 7) & 15u) << 3) | dir);
+                uint32_t dir, nb;
+                if (SHADOW) {
+                    dir = pk & DIR_MASK;
+                    nb = pk & 0x7Fu;
+                } else {
+                    const uint32_t mask = pk & 63u;
+                    dir = DIR_NONE;
+                    if (pk & 64u) dir = slot_to_dir_fast(mask, uniform_from(x[k], y[k], popc6(mask) + (TOPO == IMP3D ? 1u : 0u)));
+                    nb = (((pk >> 7) & 15u) << 3) | dir;
+                }
+                if (valid) reinterpret_cast<uint8_t*>(L.out)[jl] = (uint8_t)nb;
                 if (TOPO == IMP3D) {
                     const unsigned long long bits = __ballot(valid && dir == DIR_RANDOM);
                     if (lane == 0) {  // the slab's first tile may start below lo: no word there
@@ -766,8 +827,14 @@ __device__ __forceinline__ void ps_tiles(const RoundArgs& a, uint32_t r, TileLds
             }
         }
         };
-        if (full) tile_body(std::true_type{});
-        else tile_body(std::false_type{});
+#ifdef GP_EXPERIMENTS
+        if (!a.slot_shadow) {  // GP_SLOT_SHADOW=0: the batch draw at the tile's end, every slot decided at its start (A/B)
+            if (full) tile_body(std::true_type{}, std::false_type{});
+            else tile_body(std::false_type{}, std::false_type{});
+        } else
+#endif
+        if (full) tile_body(std::true_type{}, std::true_type{});
+        else tile_body(std::false_type{}, std::true_type{});
         // no barrier here: the next tile's in-edge pass and staging copies write
         // bits / msg / rows / xm / xp / ind, none of which this byte output reads,
         // and its node phase writes L.out only after its staging barrier

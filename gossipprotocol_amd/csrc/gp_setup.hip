@@ -61,6 +61,7 @@ ExpOverrides read_overrides() {
     o.xcap = count("GP_XCAP", 1);
     o.no_pack = is_one("GP_NO_PACK");
     o.ind4_wide = count("GP_IND4_WIDE", 1);
+    o.slot_shadow = is_one("GP_SLOT_SHADOW");
     o.force_rccl = is_one("GP_FORCE_RCCL");
     o.check_close = exp_env("GP_CHECK_CLOSE") != nullptr;
     return o;
@@ -301,6 +302,7 @@ int build_sim(gp_sim* s) {
         }
 #ifdef GP_EXPERIMENTS
         sl.S.tile_no_full = kp.no_full;
+        sl.S.tile_slot_shadow = s->exp.slot_shadow.value_or(true) ? 1u : 0u;
 #endif
         if ((rc = alloc_slab(s, sl, sl.rank))) return rc;
         sl.S.rregions = kp.rregions;

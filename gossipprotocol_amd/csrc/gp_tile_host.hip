@@ -63,6 +63,7 @@ RoundArgs make_round_args(const DevState& S, uint32_t round) {
     a.stage_cap = S.tile_stage_cap;
 #ifdef GP_EXPERIMENTS
     a.no_full = S.tile_no_full;
+    a.slot_shadow = S.tile_slot_shadow;
 #endif
     a.wx = S.tile_wx;
     a.fuse = S.fuse_finalize;
