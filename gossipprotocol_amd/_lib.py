@@ -63,6 +63,17 @@ class GpFaultStats(C.Structure):
     _fields_ = [("doomed", C.c_int64), ("down", C.c_int64), ("threshold", C.c_int64), ("lost", C.c_int64)]
 
 
+class GpTraceRow(C.Structure):
+    """One row of an ensemble member's trace (gp_trace_row)."""
+    _fields_ = [("round", C.c_int64), ("reached", C.c_uint32), ("alerts", C.c_uint32), ("sent", C.c_uint64),
+                ("err_max", C.c_double)]
+
+
+class GpTraceCfg(C.Structure):
+    """Trace parameters of an ensemble (gp_trace_cfg)."""
+    _fields_ = [("stride", C.c_int64), ("capacity", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
 class GpSummary(C.Structure):
     """What a run computed, reduced on the device (gp_summary)."""
     _fields_ = [("first", C.c_int64), ("count", C.c_int64), ("population", C.c_int64), ("rounds", C.c_int64),
@@ -128,6 +139,11 @@ SIGNATURES = [
     ("gp_ensemble_create_faults", _i32, [C.POINTER(GpConfig), C.POINTER(GpFaults), C.POINTER(C.c_uint64), _i64,
                                          C.POINTER(_vp)]),
     ("gp_ensemble_fault_stats", _i32, [_vp, C.POINTER(GpFaultStats)]),
+    ("gp_ensemble_trace_max_nodes", _i64, [_i32, _i32, _i32]),
+    ("gp_ensemble_create_traced", _i32, [C.POINTER(GpConfig), C.POINTER(GpFaults), C.POINTER(GpTraceCfg),
+                                         C.POINTER(C.c_uint64), _i64, C.POINTER(_vp)]),
+    ("gp_ensemble_trace_rows", _i32, [_vp, C.POINTER(_i64)]),
+    ("gp_ensemble_trace_read", _i32, [_vp, _i64, _i64, _i64, _vp]),
     ("gp_summary_take", _i32, [_vp, C.c_double, _i32, C.POINTER(GpSummary)]),
     ("gp_summary_merge", _i32, [C.POINTER(GpSummary), C.POINTER(GpSummary), C.POINTER(GpSummary)]),
     ("gp_ensemble_summary", _i32, [_vp, C.c_double, C.POINTER(GpSummary)]),

@@ -67,6 +67,24 @@ int64_t faults_max_nodes(int topo, int alg) {
     return table[topo][alg];
 }
 
+// The same for the trace layout (the trace block), without and with the failure model.
+int64_t trace_max_nodes(int topo, int alg, bool faults) {
+    static constexpr int64_t table[2][4][2] = {
+        {{ens_max_nodes(LINE, GOSSIP, false, true), ens_max_nodes(LINE, PUSHSUM, false, true)},
+         {ens_max_nodes(FULL, GOSSIP, false, true), ens_max_nodes(FULL, PUSHSUM, false, true)},
+         {ens_max_nodes(GRID3D, GOSSIP, false, true), ens_max_nodes(GRID3D, PUSHSUM, false, true)},
+         {ens_max_nodes(IMP3D, GOSSIP, false, true), ens_max_nodes(IMP3D, PUSHSUM, false, true)}},
+        {{ens_max_nodes(LINE, GOSSIP, true, true), ens_max_nodes(LINE, PUSHSUM, true, true)},
+         {ens_max_nodes(FULL, GOSSIP, true, true), ens_max_nodes(FULL, PUSHSUM, true, true)},
+         {ens_max_nodes(GRID3D, GOSSIP, true, true), ens_max_nodes(GRID3D, PUSHSUM, true, true)},
+         {ens_max_nodes(IMP3D, GOSSIP, true, true), ens_max_nodes(IMP3D, PUSHSUM, true, true)}},
+    };
+    return table[faults ? 1 : 0][topo][alg];
+}
+
+// A trace buffer may take this much HBM (nseeds x capacity rows of 32 bytes).
+constexpr int64_t ENS_TRACE_BYTES_MAX = 1ll << 30;
+
 // p in [0, 1] -> q = floor(p * 2^32), exact in double; an event happens iff x < q.
 uint64_t fault_threshold(double p) { return (uint64_t)std::floor(p * 4294967296.0); }
 
@@ -90,6 +108,9 @@ struct gp_ensemble {
     uint64_t q_node = 0, q_drop = 0;
     EnsFaultRec* d_frec = nullptr;
     std::vector<EnsFaultRec> frec;  // host copy, refreshed after every launch
+    // trace (gp_ensemble_create_traced; SRS v1-T): rows stay on the device until read
+    bool traced = false;
+    EnsTrace tr{};  // capacity resolved (never 0 for "everything")
 };
 
 namespace {
@@ -115,19 +136,28 @@ int launch(gp_ensemble* e, int64_t nrounds, bool init) {
     HIP_TRY(hipMemcpyAsync(e->d_idx, e->running.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     e->args.nrounds = nrounds;
     e->args.init = init ? 1 : 0;
+    EnsFaultArgs f{};
     if (e->faults) {
-        EnsFaultArgs f{};
         f.a = e->args;
         f.frec = e->d_frec;
         f.q_node = e->q_node;
         f.q_drop = e->q_drop;
         f.fail_round = e->fp.fail_round;
+    }
+    if (e->traced) {
+        if (e->faults) {
+            HIP_TRY(ens_trace_launch(e->cfg.topology, e->cfg.algorithm, EnsTraceFaultArgs{f, e->tr}, (uint32_t)n, e->stream));
+        } else {
+            HIP_TRY(ens_trace_launch(e->cfg.topology, e->cfg.algorithm, EnsTraceArgs{e->args, e->tr}, (uint32_t)n, e->stream));
+        }
+    } else if (e->faults) {
         HIP_TRY(ens_faults_launch(e->cfg.topology, e->cfg.algorithm, f, (uint32_t)n, e->stream));
-        HIP_TRY(hipMemcpyAsync(e->frec.data(), e->d_frec, e->frec.size() * sizeof(EnsFaultRec), hipMemcpyDeviceToHost,
-                                   e->stream));
     } else {
         HIP_TRY(ens_launch(e->cfg.topology, e->cfg.algorithm, e->args, (uint32_t)n, e->stream));
     }
+    if (e->faults)
+        HIP_TRY(hipMemcpyAsync(e->frec.data(), e->d_frec, e->frec.size() * sizeof(EnsFaultRec), hipMemcpyDeviceToHost,
+                                   e->stream));
     HIP_TRY(hipMemcpyAsync(e->rec.data(), e->args.rec, e->rec.size() * sizeof(gp_member), hipMemcpyDeviceToHost,
                                e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -143,9 +173,16 @@ int create(gp_ensemble* e, const uint64_t* seeds) {
     const size_t n = (size_t)e->nseeds, P = (size_t)e->P;
     HIP_TRY(hipSetDevice(e->cfg.device));
     HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    HIP_TRY(e->faults ? ens_faults_setup(topo, alg, (uint32_t)P) : ens_setup(topo, alg, (uint32_t)P));
+    HIP_TRY(e->traced   ? ens_trace_setup(topo, alg, (uint32_t)P, e->faults)
+            : e->faults ? ens_faults_setup(topo, alg, (uint32_t)P)
+                        : ens_setup(topo, alg, (uint32_t)P));
     EnsArgs& a = e->args;
     int rc = ens_alloc(e, &a.rec, n);
+    if (!rc && e->traced) {
+        // (the kernels write a row before anybody may read it, and the set-up launch every record)
+        rc = ens_alloc(e, &e->tr.rows, n * (size_t)e->tr.capacity);
+        if (!rc) rc = ens_alloc(e, &e->tr.trec, n);
+    }
     if (!rc && e->faults) {
         rc = ens_alloc(e, &e->d_frec, n);
         e->frec.assign(n, EnsFaultRec{});  // (the set-up launch writes every record)
@@ -190,9 +227,32 @@ int64_t gp_ensemble_max_nodes(int32_t topology, int32_t algorithm) {
     return max_nodes(topology, algorithm);
 }
 
-// gp_ensemble_create and gp_ensemble_create_faults (faults != null, already checked).
-static int ensemble_create(const gp_config* cfg, const gp_faults* faults, const uint64_t* seeds, int64_t nseeds,
-                           gp_ensemble** out) {
+// gp_ensemble_create_faults' checks of the failure model.
+static int faults_ok(const char* who, const gp_faults* faults) {
+    // (the negated comparisons also refuse NaN)
+    if (!(faults->node_fail >= 0.0 && faults->node_fail <= 1.0)) {
+        set_err("%s: node_fail must be in [0, 1] (got %g)", who, faults->node_fail);
+        return GP_EINVAL;
+    }
+    if (!(faults->msg_drop >= 0.0 && faults->msg_drop <= 1.0)) {
+        set_err("%s: msg_drop must be in [0, 1] (got %g)", who, faults->msg_drop);
+        return GP_EINVAL;
+    }
+    if (faults->fail_round < 0) {
+        set_err("%s: fail_round must be >= 0 (got %lld)", who, (long long)faults->fail_round);
+        return GP_EINVAL;
+    }
+    if (faults->reserved != 0) {
+        set_err("%s: reserved must be 0 (got %lld)", who, (long long)faults->reserved);
+        return GP_EINVAL;
+    }
+    return GP_OK;
+}
+
+// gp_ensemble_create, gp_ensemble_create_faults (faults != null) and gp_ensemble_create_traced
+// (trace != null), their own arguments already checked.
+static int ensemble_create(const gp_config* cfg, const gp_faults* faults, const gp_trace_cfg* trace,
+                           const uint64_t* seeds, int64_t nseeds, gp_ensemble** out) {
     if (!seeds) {
         set_err("gp_ensemble_create: seeds is null");
         return GP_EINVAL;
@@ -216,11 +276,27 @@ static int ensemble_create(const gp_config* cfg, const gp_faults* faults, const 
         set_err("gp_ensemble_create: a population of %lld has no edge", (long long)P);
         return GP_EINVAL;
     }
-    const int64_t cap = faults ? faults_max_nodes(cfg->topology, cfg->algorithm) : max_nodes(cfg->topology, cfg->algorithm);
+    const int64_t cap = trace    ? trace_max_nodes(cfg->topology, cfg->algorithm, faults != nullptr)
+                        : faults ? faults_max_nodes(cfg->topology, cfg->algorithm)
+                                 : max_nodes(cfg->topology, cfg->algorithm);
     if (cfg->num_nodes > cap) {
-        set_err("gp_ensemble_create: num_nodes %lld exceeds the ensemble cap %lld of this pair (one workgroup's LDS%s); "
-                "use gp_create", (long long)cfg->num_nodes, (long long)cap, faults ? ", failure layout" : "");
+        set_err("gp_ensemble_create: num_nodes %lld exceeds the ensemble cap %lld of this pair (one workgroup's LDS%s%s); "
+                "use gp_create", (long long)cfg->num_nodes, (long long)cap, faults ? ", failure layout" : "",
+                trace ? ", trace layout" : "");
         return GP_EINVAL;
+    }
+    int64_t capacity = 0;
+    if (trace) {
+        capacity = trace->capacity ? trace->capacity : cfg->max_rounds / trace->stride;
+        const int64_t rows_max = ENS_TRACE_BYTES_MAX / (int64_t)sizeof(gp_trace_row) / nseeds;
+        if (capacity > rows_max) {
+            // floor(max_rounds / stride) <= rows_max  <=>  stride >= floor(max_rounds / (rows_max + 1)) + 1
+            set_err("gp_ensemble_create_traced: %lld members x %lld rows x %zu bytes exceed the trace buffer's 1 GiB; "
+                    "at most %lld rows per member fit: the smallest stride that records every row (capacity 0) is %lld",
+                    (long long)nseeds, (long long)capacity, sizeof(gp_trace_row), (long long)rows_max,
+                    (long long)(cfg->max_rounds / (rows_max + 1) + 1));
+            return GP_EINVAL;
+        }
     }
     const int rc_dev = check_device(cfg->device);
     if (rc_dev) return rc_dev;
@@ -242,6 +318,11 @@ static int ensemble_create(const gp_config* cfg, const gp_faults* faults, const 
         e->q_node = fault_threshold(faults->node_fail);
         e->q_drop = fault_threshold(faults->msg_drop);
     }
+    if (trace) {
+        e->traced = true;
+        e->tr.stride = trace->stride;
+        e->tr.capacity = capacity;
+    }
     const int rc = create(e, seeds);
     if (rc) {
         gp_ensemble_destroy(e);  // (hipFree does not touch the error message)
@@ -257,7 +338,7 @@ int gp_ensemble_create(const gp_config* cfg, const uint64_t* seeds, int64_t nsee
         return GP_EINVAL;
     }
     *out = nullptr;
-    return ensemble_create(cfg, nullptr, seeds, nseeds, out);
+    return ensemble_create(cfg, nullptr, nullptr, seeds, nseeds, out);
 }
 
 int64_t gp_ensemble_faults_max_nodes(int32_t topology, int32_t algorithm) {
@@ -276,24 +357,90 @@ int gp_ensemble_create_faults(const gp_config* cfg, const gp_faults* faults, con
         set_err("gp_ensemble_create_faults: faults is null");
         return GP_EINVAL;
     }
-    // (the negated comparisons also refuse NaN)
-    if (!(faults->node_fail >= 0.0 && faults->node_fail <= 1.0)) {
-        set_err("gp_ensemble_create_faults: node_fail must be in [0, 1] (got %g)", faults->node_fail);
+    if (faults_ok("gp_ensemble_create_faults", faults)) return GP_EINVAL;
+    return ensemble_create(cfg, faults, nullptr, seeds, nseeds, out);
+}
+
+int64_t gp_ensemble_trace_max_nodes(int32_t topology, int32_t algorithm, int32_t faults) {
+    if (!pair_ok(topology, algorithm)) return GP_EINVAL;
+    return trace_max_nodes(topology, algorithm, faults != 0);
+}
+
+int gp_ensemble_create_traced(const gp_config* cfg, const gp_faults* faults, const gp_trace_cfg* trace,
+                              const uint64_t* seeds, int64_t nseeds, gp_ensemble** out) {
+    if (!cfg || !out) {
+        set_err("gp_ensemble_create_traced: null argument");
         return GP_EINVAL;
     }
-    if (!(faults->msg_drop >= 0.0 && faults->msg_drop <= 1.0)) {
-        set_err("gp_ensemble_create_faults: msg_drop must be in [0, 1] (got %g)", faults->msg_drop);
+    *out = nullptr;
+    if (!trace) {
+        set_err("gp_ensemble_create_traced: trace is null");
         return GP_EINVAL;
     }
-    if (faults->fail_round < 0) {
-        set_err("gp_ensemble_create_faults: fail_round must be >= 0 (got %lld)", (long long)faults->fail_round);
+    if (trace->stride < 1) {
+        set_err("gp_ensemble_create_traced: stride must be >= 1 (got %lld)", (long long)trace->stride);
         return GP_EINVAL;
     }
-    if (faults->reserved != 0) {
-        set_err("gp_ensemble_create_faults: reserved must be 0 (got %lld)", (long long)faults->reserved);
+    if (trace->capacity < 0) {
+        set_err("gp_ensemble_create_traced: capacity must be >= 0 (got %lld)", (long long)trace->capacity);
         return GP_EINVAL;
     }
-    return ensemble_create(cfg, faults, seeds, nseeds, out);
+    if (trace->reserved[0] != 0 || trace->reserved[1] != 0) {
+        set_err("gp_ensemble_create_traced: reserved must be 0 (got %lld, %lld)", (long long)trace->reserved[0],
+                (long long)trace->reserved[1]);
+        return GP_EINVAL;
+    }
+    if (faults && faults_ok("gp_ensemble_create_traced", faults)) return GP_EINVAL;
+    return ensemble_create(cfg, faults, trace, seeds, nseeds, out);
+}
+
+// Rows member m has recorded: a pure function of its record, no counter lives on the device.
+static int64_t trace_rows_of(const gp_ensemble* e, size_t m) {
+    return std::min(e->tr.capacity, e->rec[m].rounds / e->tr.stride);
+}
+
+int gp_ensemble_trace_rows(gp_ensemble* e, int64_t* rows_out) {
+    if (!e || !rows_out) {
+        set_err("gp_ensemble_trace_rows: null argument");
+        return GP_EINVAL;
+    }
+    if (!e->traced) {
+        set_err("gp_ensemble_trace_rows: the ensemble records no trace (gp_ensemble_create_traced does)");
+        return GP_ESTATE;
+    }
+    for (int64_t m = 0; m < e->nseeds; ++m) rows_out[m] = trace_rows_of(e, (size_t)m);
+    return GP_OK;
+}
+
+int gp_ensemble_trace_read(gp_ensemble* e, int64_t member, int64_t first, int64_t count, gp_trace_row* out) {
+    if (!e) {
+        set_err("gp_ensemble_trace_read: null handle");
+        return GP_EINVAL;
+    }
+    if (!e->traced) {
+        set_err("gp_ensemble_trace_read: the ensemble records no trace (gp_ensemble_create_traced does)");
+        return GP_ESTATE;
+    }
+    if (member < 0 || member >= e->nseeds) {
+        set_err("gp_ensemble_trace_read: member %lld outside %lld members", (long long)member, (long long)e->nseeds);
+        return GP_EINVAL;
+    }
+    const int64_t have = trace_rows_of(e, (size_t)member);
+    if (first < 0 || count < 0 || first > have || count > have - first) {
+        set_err("gp_ensemble_trace_read: rows [%lld, +%lld) outside the %lld rows member %lld has recorded",
+                (long long)first, (long long)count, (long long)have, (long long)member);
+        return GP_EINVAL;
+    }
+    if (count == 0) return GP_OK;
+    if (!out) {
+        set_err("gp_ensemble_trace_read: out is null");
+        return GP_EINVAL;
+    }
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    const gp_trace_row* src = e->tr.rows + ((size_t)member * (size_t)e->tr.capacity + (size_t)first);
+    HIP_TRY(hipMemcpyAsync(out, src, (size_t)count * sizeof(gp_trace_row), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return GP_OK;
 }
 
 int gp_ensemble_fault_stats(gp_ensemble* e, gp_fault_stats* out) {

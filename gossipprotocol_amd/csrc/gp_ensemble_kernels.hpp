@@ -4,10 +4,13 @@
 // traffic in the round loop.  Workgroups never talk to each other; a grid larger
 // than what is resident simply queues.  DESIGN.md §9; layout: gp_ensemble.hpp.
 //
-// Included by exactly two translation units, which instantiate the templates:
-// gp_ensemble.hip with FAULTS = false (the plain kernels) and gp_ensemble_faults.hip
-// with FAULTS = true (crashed nodes and lost messages, SRS v1-F).
-// Every line a fault adds sits under `if (FAULTS)`, a compile-time branch.
+// Included by exactly three translation units, which instantiate the templates:
+// gp_ensemble.hip with FAULTS = false (the plain kernels), gp_ensemble_faults.hip
+// with FAULTS = true (crashed nodes and lost messages, SRS v1-F) and
+// gp_ensemble_trace.hip with TRACE = true for both values of FAULTS (a row per
+// stride rounds, SRS v1-T; the other two keep TRACE = false).
+// Every line a fault adds sits under `if (FAULTS)`, every line tracing adds under
+// `if constexpr (TRACE)`, compile-time branches.
 //
 // The rounds are SRS v1 exactly as the per-round kernels
 // and the oracle run them: same Philox draws (gp_device.hpp), push-sum folded own
@@ -24,16 +27,31 @@
 namespace gp {
 namespace {
 
-template <bool FAULTS>
+template <bool FAULTS, bool TRACE = false>
 struct EnsKernelArgs {
     using type = EnsArgs;
 };
 template <>
-struct EnsKernelArgs<true> {
+struct EnsKernelArgs<true, false> {
     using type = EnsFaultArgs;
 };
+template <>
+struct EnsKernelArgs<false, true> {
+    using type = EnsTraceArgs;
+};
+template <>
+struct EnsKernelArgs<true, true> {
+    using type = EnsTraceFaultArgs;
+};
+// ens_model: the arguments without the trace (EnsArgs or EnsFaultArgs); ens_base: the plain ones.
+__host__ __device__ __forceinline__ const EnsArgs& ens_model(const EnsArgs& a) { return a; }
+__host__ __device__ __forceinline__ const EnsFaultArgs& ens_model(const EnsFaultArgs& f) { return f; }
+__host__ __device__ __forceinline__ const EnsArgs& ens_model(const EnsTraceArgs& t) { return t.a; }
+__host__ __device__ __forceinline__ const EnsFaultArgs& ens_model(const EnsTraceFaultArgs& t) { return t.a; }
 __host__ __device__ __forceinline__ const EnsArgs& ens_base(const EnsArgs& a) { return a; }
 __host__ __device__ __forceinline__ const EnsArgs& ens_base(const EnsFaultArgs& f) { return f.a; }
+__host__ __device__ __forceinline__ const EnsArgs& ens_base(const EnsTraceArgs& t) { return t.a; }
+__host__ __device__ __forceinline__ const EnsArgs& ens_base(const EnsTraceFaultArgs& t) { return t.a.a; }
 
 struct Member {
     uint32_t k0, k1;  // Philox key, wave-uniform
@@ -145,6 +163,72 @@ __device__ __forceinline__ void faults_end(const EnsFaultArgs& f, uint32_t m, ui
     }
 }
 
+// ------------------------------------------------------------------ trace (SRS v1-T)
+// Which round records the next row: workgroup-uniform scalars, no division in the round loop.
+struct TraceClock {
+    int64_t next_round;  // the next multiple of stride above the member's rounds
+    int64_t row;         // its row index, next_round / stride - 1
+};
+__device__ __forceinline__ TraceClock trace_begin(const EnsTrace& t, const Member& M) {
+    const int64_t k = M.rounds / t.stride;
+    return TraceClock{(k + 1) * t.stride, k};
+}
+// Does the round that starts with M.rounds completed record a row?
+__device__ __forceinline__ bool trace_records(const EnsTrace& t, const TraceClock& K, const Member& M) {
+    return M.rounds + 1 == K.next_round && K.row < t.capacity;
+}
+// Thread 0, before the barrier that ends the set-up: sent continues from the member's record.
+__device__ __forceinline__ void trace_clear(const EnsTrace& t, uint32_t m, bool init, EnsTraceLds* tr) {
+    tr->sent = init ? 0ull : (unsigned long long)t.trec[m].sent;
+    tr->err = 0;
+    tr->reached = 0;
+}
+// The threads' counts into an LDS word: one wave reduction, one LDS atomic per wave.
+__device__ __forceinline__ void trace_add32(uint32_t* word, uint32_t v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((threadIdx.x & 63u) == 0 && v) atomicAdd(word, v);
+}
+__device__ __forceinline__ void trace_add64(unsigned long long* word, uint32_t v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((threadIdx.x & 63u) == 0 && v) atomicAdd(word, (unsigned long long)v);
+}
+__device__ __forceinline__ void trace_max64(unsigned long long* word, unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_xor(v, off, 64);
+        v = o > v ? o : v;
+    }
+    if ((threadIdx.x & 63u) == 0 && v) atomicMax(word, v);
+}
+// |e| of one push-sum node as its bit pattern, e = fl(fl(s / w) - mu): no floating-point
+// comparison decides anything (a weight that underflowed to 0 gives inf or NaN).
+__device__ __forceinline__ unsigned long long trace_err_bits(double s, double w, double mu) {
+    const double e = s / w - mu;
+    return (unsigned long long)__double_as_longlong(e) & 0x7FFFFFFFFFFFFFFFull;
+}
+// One lane, after the round's closing barrier: the row of the round just completed.
+__device__ __forceinline__ void trace_row(const EnsTrace& t, uint32_t m, const TraceClock& K, const Member& M,
+                                          const EnsTraceLds* tr) {
+    gp_trace_row* row = t.rows + ((size_t)m * (size_t)t.capacity + (size_t)K.row);
+    unsigned long long e = tr->err;
+    if (e > 0x7FF0000000000000ull) e = 0x7FF8000000000000ull;  // any NaN: the canonical quiet one
+    row->round = M.rounds;
+    row->reached = tr->reached;
+    row->alerts = M.alerts;
+    row->sent = tr->sent;
+    row->err_max = __longlong_as_double((long long)e);
+}
+// End of a launch: what the threads still hold goes into the total, which the record keeps.
+// (If the last round recorded a row, every thread flushed there and adds nothing here, so
+// thread 0's read of the total for that row is not disturbed.)
+__device__ __forceinline__ void trace_end(const EnsTrace& t, uint32_t m, uint32_t nsent, EnsTraceLds* tr) {
+    trace_add64(&tr->sent, nsent);
+    __syncthreads();
+    if (threadIdx.x == 0) t.trec[m].sent = tr->sent;
+}
+
 // ------------------------------------------------------------------ gossip
 // Per round (SRS v1 B.3): phase 1 every sending node draws a neighbour and bumps
 // inc[target] iff the target is unconverged in c, which nobody writes in this phase
@@ -152,9 +236,12 @@ __device__ __forceinline__ void faults_end(const EnsFaultArgs& f, uint32_t m, ui
 // FAULTS (B.5): a down node neither sends nor receives (the injector drops it from
 // its list like a converged one), so its c stays frozen; a sender's message may be
 // dropped; alerts of doomed nodes are not counted.
-template <int TOPO, bool FAULTS>
-__global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKernelArgs<FAULTS>::type A) {
+// TRACE (SRS v1-T): reached = nodes with c >= 1 or the seed node, bumped in phase 2; sent
+// counted per thread in phase 1 and flushed before the closing barrier of a recording round.
+template <int TOPO, bool FAULTS, bool TRACE = false>
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKernelArgs<FAULTS, TRACE>::type KA) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const auto& A = ens_model(KA);
     const EnsArgs& a = ens_base(A);
     const uint32_t P = a.G.P, tid = threadIdx.x, nthr = blockDim.x;
     uint32_t* hdr = reinterpret_cast<uint32_t*>(lds);
@@ -168,6 +255,8 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKe
     uint32_t* bits = reinterpret_cast<uint32_t*>(at);
     if (TOPO != FULL) at += ens_up8(4 * ((P + 31) / 32));
     uint32_t* dm = reinterpret_cast<uint32_t*>(at);  // FAULTS: doomed bitmap
+    if (FAULTS) at += ens_up8(4 * ((P + 31) / 32));
+    EnsTraceLds* tr = reinterpret_cast<EnsTraceLds*>(at);  // TRACE: trace block
 
     const uint32_t m = a.idx[blockIdx.x];
     Member M = member_begin(a, m);
@@ -175,10 +264,12 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKe
     uint32_t* gbits = TOPO == FULL ? nullptr : a.bits + (size_t)m * a.nwords;
     uint32_t thr = a.G.T, lost = 0;
     if constexpr (FAULTS) faults_clear(hdr);
+    uint32_t nsent = 0, nreached = 0;  // TRACE: this thread's messages not yet in tr->sent; its nodes that know the rumour
 
     for (uint32_t i = tid; i < P; i += nthr) {
         c[i] = a.init ? 0 : gc[i];  // rumours = 0 (Program.fs:68)
         inc[i] = 0;
+        if constexpr (TRACE) nreached += (i == M.seed_node || c[i] >= 1) ? 1u : 0u;
         // Imp3D random neighbour: Random().Next(0, nodes-1) -> [0, P-2] (Program.fs:259)
         if (TOPO == IMP3D) rnd[i] = (uint16_t)uniform(M.k0, M.k1, S_TOPO, i, 0, P - 1);
         if constexpr (FAULTS) faults_draw(A, M, i, dm, hdr);
@@ -190,18 +281,29 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKe
             bits[q] = a.init ? (rest >= 32 ? 0xFFFFFFFFu : (1u << rest) - 1u) : gbits[q];
         }
     if (tid == 0) hdr[0] = M.alerts;
+    if constexpr (TRACE)
+        if (tid == 0) trace_clear(KA.t, m, a.init, tr);
     __syncthreads();
     if constexpr (FAULTS) thr = faults_threshold(A, hdr);
+    TraceClock K{};
+    if constexpr (TRACE) {
+        // the recount of the loaded state; phase 2 adds to it only after a later barrier
+        trace_add32(&tr->reached, nreached);
+        K = trace_begin(KA.t, M);
+    }
 
     for (int64_t it = 0; it < M.left && M.alerts < thr; ++it) {
         const uint32_t r = (uint32_t)M.rounds;
         bool down_now = false;  // are the doomed nodes down in this round?  (workgroup-uniform)
         if constexpr (FAULTS) down_now = M.rounds >= A.fail_round;
+        bool rec_now = false;  // does this round record a row?  (workgroup-uniform)
+        if constexpr (TRACE) rec_now = trace_records(KA.t, K, M);
         for (uint32_t i = tid; i < P; i += nthr) {
             const int32_t ci = c[i];
             if (!((i == M.seed_node || ci >= 1) && ci <= 10)) continue;  // Program.fs:85
             if constexpr (FAULTS)
                 if (down_now && faults_bit(dm, i)) continue;  // (c <= 10 alone would let it send)
+            if constexpr (TRACE) nsent += 1;  // it draws a target: sent, whatever becomes of the message
             uint32_t t;
             if (TOPO == FULL) {
                 t = full_target(i, uniform(M.k0, M.k1, S_GOSSIP, i, r, P - 1));
@@ -273,17 +375,34 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKe
                 if constexpr (FAULTS) counted = !faults_bit(dm, j);
                 if (counted) atomicAdd(&hdr[0], 1u);
             }
+            if constexpr (TRACE)
+                if (c0 == 0 && j != M.seed_node) atomicAdd(&tr->reached, 1u);  // (d > 0: it knows the rumour now)
             c[j] = c1;
             inc[j] = 0;
+        }
+        if constexpr (TRACE) {
+            // in this phase, not phase 1: thread 0 may still be reading the last row's total there
+            if (rec_now) {
+                trace_add64(&tr->sent, nsent);
+                nsent = 0;
+            }
         }
         __syncthreads();
         M.alerts = hdr[0];
         M.rounds += 1;
+        if constexpr (TRACE) {
+            if (rec_now && tid == 0) trace_row(KA.t, m, K, M, tr);
+            if (M.rounds == K.next_round) {
+                K.next_round += KA.t.stride;
+                K.row += 1;
+            }
+        }
     }
 
     for (uint32_t i = tid; i < P; i += nthr) gc[i] = c[i];
     if (TOPO != FULL)
         for (uint32_t q = tid; q < a.nwords; q += nthr) gbits[q] = bits[q];
+    if constexpr (TRACE) trace_end(KA.t, m, nsent, tr);
     if constexpr (FAULTS) faults_end(A, m, lost, hdr);
     member_end(a, m, M, thr);  // (thread 0 is in wave 0, which counted the injector's removals)
 }
@@ -299,12 +418,16 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKe
 // FAULTS (B.5): a down node is skipped in both phases (its registers stay as they
 // are); a sender whose message is dropped or addressed to a down node halves itself
 // but publishes DIR_NONE and hooks into no list, so no receiver ever sees it.
-template <int TOPO, int NPT, bool FAULTS>
-__global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsKernelArgs<FAULTS>::type A) {
+// TRACE (SRS v1-T): reached = nodes with the active bit, bumped in phase B; sent counted
+// per thread in phase A; in a recording round thread 0 zeroes the err word in phase A and
+// every wave folds its nodes' |e| and its sent count in after phase B, before the closing barrier.
+template <int TOPO, int NPT, bool FAULTS, bool TRACE = false>
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsKernelArgs<FAULTS, TRACE>::type KA) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr bool LISTS = TOPO == FULL || TOPO == IMP3D;
     constexpr int LT = TOPO == LINE ? LINE : GRID3D;
     constexpr uint32_t F_DOOMED = 1u << 14;  // FAULTS: fl bit, node in D
+    const auto& A = ens_model(KA);
     const EnsArgs& a = ens_base(A);
     const uint32_t P = a.G.P, tid = threadIdx.x, nthr = blockDim.x;
     uint32_t* hdr = reinterpret_cast<uint32_t*>(lds);
@@ -322,6 +445,8 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsK
     uint8_t* dir = at;
     if (TOPO != FULL) at += ens_up8(P);
     uint32_t* dm = reinterpret_cast<uint32_t*>(at);  // FAULTS: doomed bitmap
+    if (FAULTS) at += ens_up8(4 * ((P + 31) / 32));
+    EnsTraceLds* tr = reinterpret_cast<EnsTraceLds*>(at);  // TRACE: trace block
 
     const uint32_t m = a.idx[blockIdx.x];
     Member M = member_begin(a, m);
@@ -330,6 +455,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsK
     uint8_t* gf = a.fl + (size_t)m * P;
     uint32_t thr = a.G.T, lost = 0;
     if constexpr (FAULTS) faults_clear(hdr);
+    uint32_t nsent = 0, nreached = 0;  // TRACE: this thread's messages not yet in tr->sent; its active nodes
 
     // fl: bit0 active, bit1 converged, bits2-3 count (the gp_read_state byte), bits 8-13 lattice mask
     double s[NPT], w[NPT];
@@ -350,6 +476,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsK
             w[q] = gw[i];
             fl[q] = gf[i];
         }
+        if constexpr (TRACE) nreached += fl[q] & 1u;
         if (TOPO != FULL) fl[q] |= ens_mask<TOPO>(i, a.G) << 8;
         if (LISTS) head[i] = ENS_NONE;
         if (TOPO == IMP3D) rnd[i] = (uint16_t)uniform(M.k0, M.k1, S_TOPO, i, 0, P - 1);
@@ -357,13 +484,27 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsK
             if (faults_draw(A, M, i, dm, hdr)) fl[q] |= F_DOOMED;
     }
     if (tid == 0) hdr[0] = M.alerts;
+    if constexpr (TRACE)
+        if (tid == 0) trace_clear(KA.t, m, a.init, tr);
     __syncthreads();
     if constexpr (FAULTS) thr = faults_threshold(A, hdr);
+    TraceClock K{};
+    const double mu = (double)(P - 1u) * 0.5;  // TRACE: the true average
+    if constexpr (TRACE) {
+        // the recount of the loaded state; phase B adds to it only after a later barrier
+        trace_add32(&tr->reached, nreached);
+        K = trace_begin(KA.t, M);
+    }
 
     for (int64_t it = 0; it < M.left && M.alerts < thr; ++it) {
         const uint32_t r = (uint32_t)M.rounds;
         bool down_now = false;  // are the doomed nodes down in this round?  (workgroup-uniform)
         if constexpr (FAULTS) down_now = M.rounds >= A.fail_round;
+        bool rec_now = false;  // does this round record a row?  (workgroup-uniform)
+        if constexpr (TRACE) {
+            rec_now = trace_records(KA.t, K, M);
+            if (rec_now && tid == 0) tr->err = 0;  // (the last row's read of it was this thread's own)
+        }
 #pragma unroll
         for (int q = 0; q < NPT; ++q) {
             const uint32_t i = tid + q * nthr;
@@ -372,6 +513,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsK
             bool sends = fl[q] & 1u;
             if constexpr (FAULTS) sends = sends && !(down_now && (fl[q] & F_DOOMED));
             if (sends) {
+                if constexpr (TRACE) nsent += 1;  // sent, whatever becomes of the message
                 uint32_t t = 0;
                 if (TOPO == FULL) {
                     d = DIR_RANDOM;
@@ -459,14 +601,39 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsK
                     }
                     fl[q] = (fl[q] & ~12u) | (cnt << 2);
                 }
+                if constexpr (TRACE)
+                    if (!(fl[q] & 1u)) atomicAdd(&tr->reached, 1u);  // active for the first time
                 fl[q] |= 1u;
             }
             s[q] = as;
             w[q] = aw;
         }
+        if constexpr (TRACE) {
+            if (rec_now) {
+                // all P nodes, down ones included (their s, w are frozen); the division is paid here only
+                unsigned long long e = 0;
+#pragma unroll
+                for (int q = 0; q < NPT; ++q) {
+                    if (tid + q * nthr >= P) continue;
+                    const unsigned long long eq = trace_err_bits(s[q], w[q], mu);
+                    e = eq > e ? eq : e;
+                }
+                trace_max64(&tr->err, e);
+                // in this phase, not phase A: thread 0 may still be reading the last row's total there
+                trace_add64(&tr->sent, nsent);
+                nsent = 0;
+            }
+        }
         __syncthreads();
         M.alerts = hdr[0];
         M.rounds += 1;
+        if constexpr (TRACE) {
+            if (rec_now && tid == 0) trace_row(KA.t, m, K, M, tr);
+            if (M.rounds == K.next_round) {
+                K.next_round += KA.t.stride;
+                K.row += 1;
+            }
+        }
     }
 
 #pragma unroll
@@ -477,6 +644,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsK
         gw[i] = w[q];
         gf[i] = (uint8_t)(fl[q] & 15u);
     }
+    if constexpr (TRACE) trace_end(KA.t, m, nsent, tr);
     if constexpr (FAULTS) faults_end(A, m, lost, hdr);
     member_end(a, m, M, thr);
 }
@@ -493,57 +661,59 @@ inline uint32_t ens_threads(int alg, uint32_t P) {
     return t > (uint32_t)ENS_THREADS ? (uint32_t)ENS_THREADS : t;
 }
 
-template <int TOPO, bool FAULTS>
+template <int TOPO, bool FAULTS, bool TRACE = false>
 const void* ps_kernel(int npt) {
     switch (npt) {
-        case 1: return reinterpret_cast<const void*>(&k_ens_pushsum<TOPO, 1, FAULTS>);
-        case 2: return reinterpret_cast<const void*>(&k_ens_pushsum<TOPO, 2, FAULTS>);
-        case 4: return reinterpret_cast<const void*>(&k_ens_pushsum<TOPO, 4, FAULTS>);
-        case 8: return reinterpret_cast<const void*>(&k_ens_pushsum<TOPO, 8, FAULTS>);
+        case 1: return reinterpret_cast<const void*>(&k_ens_pushsum<TOPO, 1, FAULTS, TRACE>);
+        case 2: return reinterpret_cast<const void*>(&k_ens_pushsum<TOPO, 2, FAULTS, TRACE>);
+        case 4: return reinterpret_cast<const void*>(&k_ens_pushsum<TOPO, 4, FAULTS, TRACE>);
+        case 8: return reinterpret_cast<const void*>(&k_ens_pushsum<TOPO, 8, FAULTS, TRACE>);
         default: return nullptr;
     }
 }
 static_assert(ENS_NPT_MAX == 8, "ps_kernel lists the slot counts");
 
-template <bool FAULTS>
+template <bool FAULTS, bool TRACE = false>
 const void* ens_kernel(int topo, int alg, uint32_t P) {
     if (alg == GOSSIP) {
         switch (topo) {
-            case LINE: return reinterpret_cast<const void*>(&k_ens_gossip<LINE, FAULTS>);
-            case FULL: return reinterpret_cast<const void*>(&k_ens_gossip<FULL, FAULTS>);
-            case GRID3D: return reinterpret_cast<const void*>(&k_ens_gossip<GRID3D, FAULTS>);
-            case IMP3D: return reinterpret_cast<const void*>(&k_ens_gossip<IMP3D, FAULTS>);
+            case LINE: return reinterpret_cast<const void*>(&k_ens_gossip<LINE, FAULTS, TRACE>);
+            case FULL: return reinterpret_cast<const void*>(&k_ens_gossip<FULL, FAULTS, TRACE>);
+            case GRID3D: return reinterpret_cast<const void*>(&k_ens_gossip<GRID3D, FAULTS, TRACE>);
+            case IMP3D: return reinterpret_cast<const void*>(&k_ens_gossip<IMP3D, FAULTS, TRACE>);
             default: return nullptr;
         }
     }
     const int npt = ens_npt(P);
     switch (topo) {
-        case LINE: return ps_kernel<LINE, FAULTS>(npt);
-        case FULL: return ps_kernel<FULL, FAULTS>(npt);
-        case GRID3D: return ps_kernel<GRID3D, FAULTS>(npt);
-        case IMP3D: return ps_kernel<IMP3D, FAULTS>(npt);
+        case LINE: return ps_kernel<LINE, FAULTS, TRACE>(npt);
+        case FULL: return ps_kernel<FULL, FAULTS, TRACE>(npt);
+        case GRID3D: return ps_kernel<GRID3D, FAULTS, TRACE>(npt);
+        case IMP3D: return ps_kernel<IMP3D, FAULTS, TRACE>(npt);
         default: return nullptr;
     }
 }
 
-template <bool FAULTS>
+template <bool FAULTS, bool TRACE = false>
 hipError_t ens_setup_t(int topo, int alg, uint32_t P) {
-    const void* k = ens_kernel<FAULTS>(topo, alg, P);
-    if (!k || P > ens_max_population(topo, alg, FAULTS)) return hipErrorInvalidValue;  // a missing kernel is an error
-    return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ens_lds_bytes(topo, alg, P, FAULTS));
+    const void* k = ens_kernel<FAULTS, TRACE>(topo, alg, P);
+    if (!k || P > ens_max_population(topo, alg, FAULTS, TRACE)) return hipErrorInvalidValue;  // a missing kernel is an error
+    return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)ens_lds_bytes(topo, alg, P, FAULTS, TRACE));
 }
 
-template <bool FAULTS>
-hipError_t ens_launch_t(int topo, int alg, const typename EnsKernelArgs<FAULTS>::type& A, uint32_t nblocks,
+template <bool FAULTS, bool TRACE = false>
+hipError_t ens_launch_t(int topo, int alg, const typename EnsKernelArgs<FAULTS, TRACE>::type& A, uint32_t nblocks,
                         hipStream_t st) {
     const uint32_t P = ens_base(A).G.P;
-    const void* k = ens_kernel<FAULTS>(topo, alg, P);
-    if (!k || P > ens_max_population(topo, alg, FAULTS)) return hipErrorInvalidValue;
+    const void* k = ens_kernel<FAULTS, TRACE>(topo, alg, P);
+    if (!k || P > ens_max_population(topo, alg, FAULTS, TRACE)) return hipErrorInvalidValue;
     const uint32_t threads = ens_threads(alg, P);
-    if (FAULTS && threads % 64u != 0) return hipErrorInvalidValue;  // faults_draw stores whole waves' bitmap words
-    typename EnsKernelArgs<FAULTS>::type copy = A;
+    // faults_draw stores whole waves' bitmap words; the trace reduces over whole waves
+    if ((FAULTS || TRACE) && threads % 64u != 0) return hipErrorInvalidValue;
+    typename EnsKernelArgs<FAULTS, TRACE>::type copy = A;
     void* args[] = {&copy};
-    return hipLaunchKernel(k, dim3(nblocks), dim3(threads), args, ens_lds_bytes(topo, alg, P, FAULTS), st);
+    return hipLaunchKernel(k, dim3(nblocks), dim3(threads), args, ens_lds_bytes(topo, alg, P, FAULTS, TRACE), st);
 }
 
 }  // namespace

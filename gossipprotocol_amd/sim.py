@@ -190,9 +190,12 @@ class Simulation:
         return self._L.gp_alg_bytes_per_node(self._h)
 
 
-def ensemble_max_nodes(topology: str, algorithm: str, faults: bool = False) -> int:
+def ensemble_max_nodes(topology: str, algorithm: str, faults: bool = False, trace: bool = False) -> int:
     """Largest num_nodes an :class:`Ensemble` accepts for the pair (host only); faults=True:
-    the cap of an ensemble with a failure model."""
+    the cap of an ensemble with a failure model; trace=True: of one that records a trace."""
+    if trace:
+        return L.check(L.lib().gp_ensemble_trace_max_nodes(parse_topology(topology), parse_algorithm(algorithm),
+                                                           int(bool(faults))))
     f = L.lib().gp_ensemble_faults_max_nodes if faults else L.lib().gp_ensemble_max_nodes
     return L.check(f(parse_topology(topology), parse_algorithm(algorithm)))
 
@@ -210,15 +213,33 @@ class Faults:
         return f"Faults(node_fail={self.node_fail}, msg_drop={self.msg_drop}, fail_round={self.fail_round})"
 
 
+class Trace:
+    """Trace parameters of an :class:`Ensemble` (gp_trace_cfg; SRS v1-T): a
+    member that has just completed round R records a row iff R is a multiple of ``stride`` and it
+    has recorded fewer than ``capacity`` rows; capacity 0 keeps every row up to max_rounds."""
+
+    def __init__(self, stride: int = 1, capacity: int = 0):
+        self.stride, self.capacity = int(stride), int(capacity)
+
+    def __repr__(self):
+        return f"Trace(stride={self.stride}, capacity={self.capacity})"
+
+
+# one row of a trace (gp_trace_row)
+TRACE_DTYPE = np.dtype([("round", "<i8"), ("reached", "<u4"), ("alerts", "<u4"), ("sent", "<u8"), ("err_max", "<f8")])
+
+
 class Ensemble:
     """Many small networks at once on one MI355X, one per seed (handle over
     gp_ensemble): the regime of the reference's published curves, n = 100..1000
     (README.md, Report.pdf).  Each member is one workgroup with its state in LDS and
     is bit-identical to ``Simulation(num_nodes, topology, algorithm, seed)``.  With
-    ``faults=Faults(...)`` nodes crash and messages get lost (gp_ensemble_create_faults)."""
+    ``faults=Faults(...)`` nodes crash and messages get lost (gp_ensemble_create_faults); with
+    ``trace=Trace(...)`` every member records its spread curve inside the kernel
+    (gp_ensemble_create_traced), read with :meth:`trace`."""
 
     def __init__(self, num_nodes: int, topology: str, algorithm: str, seeds, max_rounds: int, device: int = 0,
-                 faults: "Faults | None" = None):
+                 faults: "Faults | None" = None, trace: "Trace | None" = None):
         self._L = L.lib()
         self.seeds = [int(s) for s in seeds]
         cfg = L.GpConfig()
@@ -232,11 +253,15 @@ class Ensemble:
         self.population = resolve(num_nodes, topology)[0]
         arr = (C.c_uint64 * max(1, len(self.seeds)))(*self.seeds)
         h = C.c_void_p()
-        self.faults = faults
-        if faults is None:
+        self.faults, self.tracing = faults, trace
+        f = None if faults is None else L.GpFaults(faults.node_fail, faults.msg_drop, faults.fail_round, 0)
+        if trace is not None:
+            t = L.GpTraceCfg(trace.stride, trace.capacity)
+            L.check(self._L.gp_ensemble_create_traced(C.byref(cfg), None if f is None else C.byref(f), C.byref(t), arr,
+                                                      len(self.seeds), C.byref(h)), self._L)
+        elif faults is None:
             L.check(self._L.gp_ensemble_create(C.byref(cfg), arr, len(self.seeds), C.byref(h)), self._L)
         else:
-            f = L.GpFaults(faults.node_fail, faults.msg_drop, faults.fail_round, 0)
             L.check(self._L.gp_ensemble_create_faults(C.byref(cfg), C.byref(f), arr, len(self.seeds), C.byref(h)),
                     self._L)
         self._h = h
@@ -292,6 +317,22 @@ class Ensemble:
         out = (L.GpFaultStats * len(self.seeds))()
         L.check(self._L.gp_ensemble_fault_stats(self._h, out), self._L)
         return list(out)
+
+    def trace_rows(self):
+        """Rows each member has recorded so far, in seed order: min(capacity, rounds // stride)."""
+        out = (C.c_int64 * len(self.seeds))()
+        L.check(self._L.gp_ensemble_trace_rows(self._h, out), self._L)
+        return list(out)
+
+    def trace(self, member: int, first: int = 0, count: int | None = None):
+        """The recorded rows [first, first + count) of one member (all from `first` on by default) as
+        a numpy structured array with the fields round, reached, alerts, sent and err_max
+        (gp_trace_row): row k is the member's state after (k + 1) * stride rounds."""
+        if count is None:
+            count = self.trace_rows()[member] - first
+        out = np.zeros(max(0, count), TRACE_DTYPE)
+        L.check(self._L.gp_ensemble_trace_read(self._h, member, first, count, out.ctypes.data), self._L)
+        return out
 
     def summary(self, tol: float = 1e-10):
         """One :class:`GpSummary` per member, in seed order, from one launch (gp_ensemble_summary);

@@ -245,6 +245,49 @@ int gp_ensemble_create_faults(const gp_config* cfg, const gp_faults* faults, con
 /* nseeds records to out.  On a plain ensemble doomed = down = lost = 0 and threshold = T. */
 int gp_ensemble_fault_stats(gp_ensemble* e, gp_fault_stats* out);
 
+/* ---- Ensemble traces: SRS v1-T -------------------------------------
+ * How a member got to its end: the S-curve of nodes reached, the messages spent, the
+ * decay of push-sum's worst estimate error, recorded inside the kernel.  A member that
+ * has just completed round R (R = 1, 2, ..., as gp_member.rounds counts) records a row
+ * iff R % stride == 0 and k = R / stride - 1 < capacity; row k is the state after R
+ * rounds, the one gp_ensemble_read_state would return if the member stopped there.  A
+ * member has recorded min(capacity, rounds / stride) rows; the initial state has none,
+ * nor has a final state whose round is no multiple of stride.  Tracing observes only:
+ * a traced member is bit-identical to the untraced one. */
+typedef struct gp_trace_row {   /* 32 bytes, blittable */
+    int64_t  round;    /* R: rounds completed when the row was taken */
+    uint32_t reached;  /* gossip: nodes that know the rumour: c >= 1, or the seed node;
+                          push-sum: nodes with flag bit0 (active), down ones included */
+    uint32_t alerts;   /* cumulative counted alerts (gp_member.converged at round R) */
+    uint64_t sent;     /* cumulative node-to-node messages sent in rounds 1..R: one per (node, round) in
+                          which the node drew a target, i.e. gossip: (seed node or c >= 1) and c <= 10 at
+                          round start; push-sum: active at round start; under the failure model: and not
+                          down in that round.  Suppressed, dropped and lost messages count (they were sent);
+                          the gossip injector's picks do not. */
+    double   err_max;  /* push-sum: max over all P nodes of |fl(fl(s/w) - mu)|, mu = (P-1)/2, exactly as
+                          gp_summary.err_max defines the term, taken as the largest 64-bit pattern with the
+                          sign bit cleared; a pattern above +inf's reads as the quiet NaN 0x7FF8000000000000.
+                          gossip: 0.0 */
+} gp_trace_row;
+typedef struct gp_trace_cfg {   /* blittable */
+    int64_t stride;             /* >= 1 */
+    int64_t capacity;           /* rows per member, >= 0; 0: floor(max_rounds / stride), i.e. every row */
+    int64_t reserved[2];        /* 0 */
+} gp_trace_cfg;
+
+/* gp_ensemble_max_nodes for a traced ensemble (host only); faults != 0: with a failure model. */
+int64_t gp_ensemble_trace_max_nodes(int32_t topology, int32_t algorithm, int32_t faults);
+/* gp_ensemble_create / _create_faults (faults may be NULL) with tracing.  Every check of those
+ * applies (against gp_ensemble_trace_max_nodes); in addition trace must be non-null, stride >= 1,
+ * capacity >= 0, reserved 0 and nseeds x capacity x 32 bytes at most 1 GiB, else GP_EINVAL.
+ * The handle works with every gp_ensemble_* call. */
+int gp_ensemble_create_traced(const gp_config* cfg, const gp_faults* faults, const gp_trace_cfg* trace,
+                              const uint64_t* seeds, int64_t nseeds, gp_ensemble** out);
+/* Rows recorded so far per member: nseeds values.  GP_ESTATE on an untraced ensemble. */
+int gp_ensemble_trace_rows(gp_ensemble* e, int64_t* rows_out);
+/* Rows [first, first+count) of one member; the range must lie within its recorded rows. */
+int gp_ensemble_trace_read(gp_ensemble* e, int64_t member, int64_t first, int64_t count, gp_trace_row* out);
+
 /* ---- State summary: what a run computed, reduced on the device ---
  * The reference never printed s/w, yet that ratio is the whole
  * output of push-sum.  gp_summary_take reduces the node state where it lives, in
