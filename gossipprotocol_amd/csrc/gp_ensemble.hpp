@@ -1,7 +1,7 @@
 // gp_ensemble.hpp -- ensemble runs (gp_ensemble.hip): one workgroup simulates one
 // whole small network in LDS, a grid of workgroups runs many seeds at once.
-// This header is the LDS layout (and with it the population cap per pair) plus
-// the host launch interface; DESIGN.md §9.
+// This header is the variant descriptor, the LDS layout (and with it the population cap
+// per pair and variant), the kernel arguments and the host launch interface; DESIGN.md §9.
 #pragma once
 
 #include <stdint.h>
@@ -20,6 +20,11 @@ constexpr uint32_t ENS_NONE = 0xFFFFu;       // end of a receiver's message list
 
 constexpr uint32_t ens_up8(uint32_t b) { return (b + 7u) & ~7u; }
 
+// Which kernels run an ensemble: with the failure model, recording a trace.
+struct EnsVariant {
+    bool faults, trace;
+};
+
 // LDS image of one member, arrays in this order, each padded to 8 bytes:
 //   gossip   : c int32[P], inc int32[P], rnd u16[P] (Imp3D), live bitmap u32[ceil(T/32)] (not full)
 //   push-sum : hs f64[P], hw f64[P] (the halves a sender offers this round), head u32[P] + next u16[P]
@@ -32,7 +37,7 @@ constexpr uint32_t ens_up8(uint32_t b) { return (b + 7u) & ~7u; }
 // The traced kernels (SRS v1-T, gp_ensemble_trace.hip) append after that
 //   trace block, ENS_LDS_TRACE bytes (EnsTraceLds): the words a row is made of
 constexpr uint32_t ENS_LDS_TRACE = 32;
-constexpr uint32_t ens_lds_bytes(int topo, int alg, uint32_t P, bool faults = false, bool trace = false) {
+constexpr uint32_t ens_lds_bytes(int topo, int alg, uint32_t P, EnsVariant v) {
     uint32_t b = ENS_LDS_HDR;
     if (alg == GOSSIP) {
         b += ens_up8(4 * P) * 2;
@@ -44,58 +49,38 @@ constexpr uint32_t ens_lds_bytes(int topo, int alg, uint32_t P, bool faults = fa
         if (topo == IMP3D) b += ens_up8(2 * P);
         if (topo != FULL) b += ens_up8(P);
     }
-    if (faults) b += ens_up8(4 * ((P + 31) / 32));
-    if (trace) b += ENS_LDS_TRACE;
+    if (v.faults) b += ens_up8(4 * ((P + 31) / 32));
+    if (v.trace) b += ENS_LDS_TRACE;
     return b;
 }
 
 // Largest population a member may have: the LDS image fits and every node has a
 // thread slot.  A compile-time function of the layout above.
-constexpr uint32_t ens_max_population(int topo, int alg, bool faults = false, bool trace = false) {
+constexpr uint32_t ens_max_population(int topo, int alg, EnsVariant v) {
     uint32_t P = (uint32_t)ENS_THREADS * ENS_NPT_MAX;
-    while (P > 2 && ens_lds_bytes(topo, alg, P, faults, trace) > ENS_LDS_MAX) --P;
+    while (P > 2 && ens_lds_bytes(topo, alg, P, v) > ENS_LDS_MAX) --P;
     return P;
 }
-static_assert(ens_max_population(IMP3D, PUSHSUM) >= 1001 && ens_max_population(FULL, PUSHSUM) >= 1001, "report range");
-static_assert(ens_max_population(IMP3D, PUSHSUM, true) >= 1001 && ens_max_population(FULL, PUSHSUM, true) >= 1001,
-              "report range, failure layout");
-static_assert(ens_max_population(LINE, GOSSIP, false, true) >= 1001 && ens_max_population(LINE, PUSHSUM, false, true) >= 1001 &&
-                  ens_max_population(FULL, GOSSIP, false, true) >= 1001 && ens_max_population(FULL, PUSHSUM, false, true) >= 1001 &&
-                  ens_max_population(GRID3D, GOSSIP, false, true) >= 1001 && ens_max_population(GRID3D, PUSHSUM, false, true) >= 1001 &&
-                  ens_max_population(IMP3D, GOSSIP, false, true) >= 1001 && ens_max_population(IMP3D, PUSHSUM, false, true) >= 1001,
-              "report range, trace layout");
-static_assert(ens_max_population(LINE, GOSSIP, true, true) >= 1001 && ens_max_population(LINE, PUSHSUM, true, true) >= 1001 &&
-                  ens_max_population(FULL, GOSSIP, true, true) >= 1001 && ens_max_population(FULL, PUSHSUM, true, true) >= 1001 &&
-                  ens_max_population(GRID3D, GOSSIP, true, true) >= 1001 && ens_max_population(GRID3D, PUSHSUM, true, true) >= 1001 &&
-                  ens_max_population(IMP3D, GOSSIP, true, true) >= 1001 && ens_max_population(IMP3D, PUSHSUM, true, true) >= 1001,
-              "report range, trace + failure layout");
+// Every variant of every pair covers the report's range.
+constexpr bool ens_covers_report_range() {
+    for (int faults = 0; faults < 2; ++faults)
+        for (int trace = 0; trace < 2; ++trace)
+            for (int topo = LINE; topo <= IMP3D; ++topo)
+                for (int alg = GOSSIP; alg <= PUSHSUM; ++alg)
+                    if (ens_max_population(topo, alg, EnsVariant{faults != 0, trace != 0}) < 1001) return false;
+    return true;
+}
+static_assert(ens_covers_report_range(), "report range");
 static_assert((uint32_t)ENS_THREADS * ENS_NPT_MAX < ENS_NONE, "node ids must fit the 16-bit list links");
 
 // Largest num_nodes: line / full P = n + 1; 3D / Imp3D the largest whole cube.
-constexpr int64_t ens_max_nodes(int topo, int alg, bool faults = false, bool trace = false) {
-    const uint32_t P = ens_max_population(topo, alg, faults, trace);
+constexpr int64_t ens_max_nodes(int topo, int alg, EnsVariant v) {
+    const uint32_t P = ens_max_population(topo, alg, v);
     if (topo == LINE || topo == FULL) return (int64_t)P - 1;
     uint32_t g = 1;
     while ((g + 1) * (g + 1) * (g + 1) <= P) ++g;
     return (int64_t)g * g * g;
 }
-
-// Kernel arguments.  rec[m] is member m's record (gp_member; `reserved` carries the
-// injector's live count between launches); idx[b] is the member workgroup b runs.
-struct EnsArgs {
-    gp_member* rec;
-    const uint32_t* idx;
-    int32_t* c;      // gossip: nseeds x P rumour counters
-    uint32_t* bits;  // gossip, not full: nseeds x nwords live bitmap of the injector
-    double* s;       // push-sum: nseeds x P
-    double* w;
-    uint8_t* fl;     // push-sum: nseeds x P, bit0 active, bit1 converged, bits2-3 count
-    Geom G;
-    uint32_t nwords;
-    int32_t init;        // 1: set the member up from its seed instead of loading it
-    int64_t nrounds;     // rounds this launch may run
-    int64_t max_rounds;  // cap on a member's total rounds
-};
 
 // Failure model (SRS v1-F): Philox streams and the per-member record
 // that persists between launches beside gp_member (whose `converged` carries the
@@ -105,10 +90,9 @@ struct EnsFaultRec {
     int64_t lost;    // messages sent that nobody received, all launches so far
     int64_t doomed;  // |D|
 };
-// Arguments of the failure kernels: the plain ones plus the failure parameters.  An
-// event with threshold q happens iff (uint64) x < q, x the first Philox output word.
-struct EnsFaultArgs {
-    EnsArgs a;
+// The failure parameters.  An event with threshold q happens iff (uint64) x < q, x the
+// first Philox output word.
+struct EnsFaults {
     EnsFaultRec* frec;
     uint64_t q_node, q_drop;  // floor(p * 2^32); 2^32 = always
     int64_t fail_round;
@@ -140,26 +124,56 @@ struct EnsTrace {
     EnsTraceRec* trec;   // nseeds
     int64_t stride, capacity;
 };
-// Arguments of the traced kernels: the plain / failure ones plus the trace.
-struct EnsTraceArgs {
-    EnsArgs a;
-    EnsTrace t;
-};
-struct EnsTraceFaultArgs {
-    EnsFaultArgs a;
+
+// Kernel arguments, the same block for every variant.  rec[m] is member m's record
+// (gp_member; `reserved` carries the injector's live count between launches); idx[b] is
+// the member workgroup b runs.  A kernel without the failure model never reads f, an
+// untraced one never reads t.
+struct EnsArgs {
+    gp_member* rec;
+    const uint32_t* idx;
+    int32_t* c;      // gossip: nseeds x P rumour counters
+    uint32_t* bits;  // gossip, not full: nseeds x nwords live bitmap of the injector
+    double* s;       // push-sum: nseeds x P
+    double* w;
+    uint8_t* fl;     // push-sum: nseeds x P, bit0 active, bit1 converged, bits2-3 count
+    Geom G;
+    uint32_t nwords;
+    int32_t init;        // 1: set the member up from its seed instead of loading it
+    int64_t nrounds;     // rounds this launch may run
+    int64_t max_rounds;  // cap on a member's total rounds
+    EnsFaults f;
     EnsTrace t;
 };
 
-// Raises the kernel's dynamic-LDS limit for population P; once per handle.
-hipError_t ens_setup(int topo, int alg, uint32_t P);
-// Plain launch, one workgroup per listed member.
-hipError_t ens_launch(int topo, int alg, const EnsArgs& a, uint32_t nblocks, hipStream_t st);
-// The same two for the failure kernels (gp_ensemble_faults.hip).
-hipError_t ens_faults_setup(int topo, int alg, uint32_t P);
-hipError_t ens_faults_launch(int topo, int alg, const EnsFaultArgs& a, uint32_t nblocks, hipStream_t st);
-// The same for the traced kernels (gp_ensemble_trace.hip), without and with the failure model.
-hipError_t ens_trace_setup(int topo, int alg, uint32_t P, bool faults);
-hipError_t ens_trace_launch(int topo, int alg, const EnsTraceArgs& a, uint32_t nblocks, hipStream_t st);
-hipError_t ens_trace_launch(int topo, int alg, const EnsTraceFaultArgs& a, uint32_t nblocks, hipStream_t st);
+// The launch interface of one variant, defined in gp_ensemble_kernels.hpp and instantiated by
+// gp_ensemble.hip (plain), gp_ensemble_faults.hip (failure) and gp_ensemble_trace.hip (both traced).
+// Setup raises the kernel's dynamic-LDS limit for population P, once per handle; launch runs
+// one workgroup per listed member.
+template <bool FAULTS, bool TRACE>
+hipError_t ens_setup_t(int topo, int alg, uint32_t P);
+template <bool FAULTS, bool TRACE>
+hipError_t ens_launch_t(int topo, int alg, const EnsArgs& a, uint32_t nblocks, hipStream_t st);
+// (extern: the dispatchers below must not instantiate every variant in every unit)
+extern template hipError_t ens_setup_t<false, false>(int, int, uint32_t);
+extern template hipError_t ens_setup_t<true, false>(int, int, uint32_t);
+extern template hipError_t ens_setup_t<false, true>(int, int, uint32_t);
+extern template hipError_t ens_setup_t<true, true>(int, int, uint32_t);
+extern template hipError_t ens_launch_t<false, false>(int, int, const EnsArgs&, uint32_t, hipStream_t);
+extern template hipError_t ens_launch_t<true, false>(int, int, const EnsArgs&, uint32_t, hipStream_t);
+extern template hipError_t ens_launch_t<false, true>(int, int, const EnsArgs&, uint32_t, hipStream_t);
+extern template hipError_t ens_launch_t<true, true>(int, int, const EnsArgs&, uint32_t, hipStream_t);
+
+inline hipError_t ens_setup(EnsVariant v, int topo, int alg, uint32_t P) {
+    if (v.trace) return v.faults ? ens_setup_t<true, true>(topo, alg, P) : ens_setup_t<false, true>(topo, alg, P);
+    return v.faults ? ens_setup_t<true, false>(topo, alg, P) : ens_setup_t<false, false>(topo, alg, P);
+}
+inline hipError_t ens_launch(EnsVariant v, int topo, int alg, const EnsArgs& a, uint32_t nblocks, hipStream_t st) {
+    if (v.trace)
+        return v.faults ? ens_launch_t<true, true>(topo, alg, a, nblocks, st)
+                        : ens_launch_t<false, true>(topo, alg, a, nblocks, st);
+    return v.faults ? ens_launch_t<true, false>(topo, alg, a, nblocks, st)
+                    : ens_launch_t<false, false>(topo, alg, a, nblocks, st);
+}
 
 }  // namespace gp

@@ -45,43 +45,6 @@ bool pair_ok(int32_t topology, int32_t algorithm) {
     return true;
 }
 
-int64_t max_nodes(int topo, int alg) {
-    // ens_max_nodes is a compile-time function of the LDS layout: one constant per pair
-    static constexpr int64_t table[4][2] = {
-        {ens_max_nodes(LINE, GOSSIP), ens_max_nodes(LINE, PUSHSUM)},
-        {ens_max_nodes(FULL, GOSSIP), ens_max_nodes(FULL, PUSHSUM)},
-        {ens_max_nodes(GRID3D, GOSSIP), ens_max_nodes(GRID3D, PUSHSUM)},
-        {ens_max_nodes(IMP3D, GOSSIP), ens_max_nodes(IMP3D, PUSHSUM)},
-    };
-    return table[topo][alg];
-}
-
-// The same for the failure layout (the doomed bitmap lowers the LDS-bound caps).
-int64_t faults_max_nodes(int topo, int alg) {
-    static constexpr int64_t table[4][2] = {
-        {ens_max_nodes(LINE, GOSSIP, true), ens_max_nodes(LINE, PUSHSUM, true)},
-        {ens_max_nodes(FULL, GOSSIP, true), ens_max_nodes(FULL, PUSHSUM, true)},
-        {ens_max_nodes(GRID3D, GOSSIP, true), ens_max_nodes(GRID3D, PUSHSUM, true)},
-        {ens_max_nodes(IMP3D, GOSSIP, true), ens_max_nodes(IMP3D, PUSHSUM, true)},
-    };
-    return table[topo][alg];
-}
-
-// The same for the trace layout (the trace block), without and with the failure model.
-int64_t trace_max_nodes(int topo, int alg, bool faults) {
-    static constexpr int64_t table[2][4][2] = {
-        {{ens_max_nodes(LINE, GOSSIP, false, true), ens_max_nodes(LINE, PUSHSUM, false, true)},
-         {ens_max_nodes(FULL, GOSSIP, false, true), ens_max_nodes(FULL, PUSHSUM, false, true)},
-         {ens_max_nodes(GRID3D, GOSSIP, false, true), ens_max_nodes(GRID3D, PUSHSUM, false, true)},
-         {ens_max_nodes(IMP3D, GOSSIP, false, true), ens_max_nodes(IMP3D, PUSHSUM, false, true)}},
-        {{ens_max_nodes(LINE, GOSSIP, true, true), ens_max_nodes(LINE, PUSHSUM, true, true)},
-         {ens_max_nodes(FULL, GOSSIP, true, true), ens_max_nodes(FULL, PUSHSUM, true, true)},
-         {ens_max_nodes(GRID3D, GOSSIP, true, true), ens_max_nodes(GRID3D, PUSHSUM, true, true)},
-         {ens_max_nodes(IMP3D, GOSSIP, true, true), ens_max_nodes(IMP3D, PUSHSUM, true, true)}},
-    };
-    return table[faults ? 1 : 0][topo][alg];
-}
-
 // A trace buffer may take this much HBM (nseeds x capacity rows of 32 bytes).
 constexpr int64_t ENS_TRACE_BYTES_MAX = 1ll << 30;
 
@@ -96,21 +59,17 @@ struct gp_ensemble {
     int64_t nseeds = 0;
     uint32_t nwords = 0;
     hipStream_t stream = nullptr;
+    // v.faults: failure model (gp_ensemble_create_faults; SRS v1-F), parameters in args.f;
+    // v.trace: trace (gp_ensemble_create_traced; SRS v1-T), in args.t with the capacity
+    // resolved (never 0 for "everything"); the rows stay on the device until read
+    EnsVariant v{};
     EnsArgs args{};
     uint32_t* d_idx = nullptr;
     std::vector<void*> allocs;
     std::vector<gp_member> rec;    // host copy of the member records, refreshed after every launch
     std::vector<uint32_t> running; // unfinished members, in member order
     SumAcc* d_sum = nullptr;       // gp_ensemble_summary: one record per member, allocated at the first call
-    // failure model (gp_ensemble_create_faults; SRS v1-F)
-    bool faults = false;
-    gp_faults fp{};
-    uint64_t q_node = 0, q_drop = 0;
-    EnsFaultRec* d_frec = nullptr;
-    std::vector<EnsFaultRec> frec;  // host copy, refreshed after every launch
-    // trace (gp_ensemble_create_traced; SRS v1-T): rows stay on the device until read
-    bool traced = false;
-    EnsTrace tr{};  // capacity resolved (never 0 for "everything")
+    std::vector<EnsFaultRec> frec; // v.faults: host copy of args.f.frec, refreshed after every launch
 };
 
 namespace {
@@ -136,28 +95,10 @@ int launch(gp_ensemble* e, int64_t nrounds, bool init) {
     HIP_TRY(hipMemcpyAsync(e->d_idx, e->running.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     e->args.nrounds = nrounds;
     e->args.init = init ? 1 : 0;
-    EnsFaultArgs f{};
-    if (e->faults) {
-        f.a = e->args;
-        f.frec = e->d_frec;
-        f.q_node = e->q_node;
-        f.q_drop = e->q_drop;
-        f.fail_round = e->fp.fail_round;
-    }
-    if (e->traced) {
-        if (e->faults) {
-            HIP_TRY(ens_trace_launch(e->cfg.topology, e->cfg.algorithm, EnsTraceFaultArgs{f, e->tr}, (uint32_t)n, e->stream));
-        } else {
-            HIP_TRY(ens_trace_launch(e->cfg.topology, e->cfg.algorithm, EnsTraceArgs{e->args, e->tr}, (uint32_t)n, e->stream));
-        }
-    } else if (e->faults) {
-        HIP_TRY(ens_faults_launch(e->cfg.topology, e->cfg.algorithm, f, (uint32_t)n, e->stream));
-    } else {
-        HIP_TRY(ens_launch(e->cfg.topology, e->cfg.algorithm, e->args, (uint32_t)n, e->stream));
-    }
-    if (e->faults)
-        HIP_TRY(hipMemcpyAsync(e->frec.data(), e->d_frec, e->frec.size() * sizeof(EnsFaultRec), hipMemcpyDeviceToHost,
-                                   e->stream));
+    HIP_TRY(ens_launch(e->v, e->cfg.topology, e->cfg.algorithm, e->args, (uint32_t)n, e->stream));
+    if (e->v.faults)
+        HIP_TRY(hipMemcpyAsync(e->frec.data(), e->args.f.frec, e->frec.size() * sizeof(EnsFaultRec),
+                                   hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(e->rec.data(), e->args.rec, e->rec.size() * sizeof(gp_member), hipMemcpyDeviceToHost,
                                e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -173,18 +114,16 @@ int create(gp_ensemble* e, const uint64_t* seeds) {
     const size_t n = (size_t)e->nseeds, P = (size_t)e->P;
     HIP_TRY(hipSetDevice(e->cfg.device));
     HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    HIP_TRY(e->traced   ? ens_trace_setup(topo, alg, (uint32_t)P, e->faults)
-            : e->faults ? ens_faults_setup(topo, alg, (uint32_t)P)
-                        : ens_setup(topo, alg, (uint32_t)P));
+    HIP_TRY(ens_setup(e->v, topo, alg, (uint32_t)P));
     EnsArgs& a = e->args;
     int rc = ens_alloc(e, &a.rec, n);
-    if (!rc && e->traced) {
+    if (!rc && e->v.trace) {
         // (the kernels write a row before anybody may read it, and the set-up launch every record)
-        rc = ens_alloc(e, &e->tr.rows, n * (size_t)e->tr.capacity);
-        if (!rc) rc = ens_alloc(e, &e->tr.trec, n);
+        rc = ens_alloc(e, &a.t.rows, n * (size_t)a.t.capacity);
+        if (!rc) rc = ens_alloc(e, &a.t.trec, n);
     }
-    if (!rc && e->faults) {
-        rc = ens_alloc(e, &e->d_frec, n);
+    if (!rc && e->v.faults) {
+        rc = ens_alloc(e, &a.f.frec, n);
         e->frec.assign(n, EnsFaultRec{});  // (the set-up launch writes every record)
     }
     if (!rc) rc = ens_alloc(e, &e->d_idx, n);
@@ -222,9 +161,9 @@ int create(gp_ensemble* e, const uint64_t* seeds) {
 
 extern "C" {
 
+// The caps are a function of the LDS layout (ens_max_nodes: a few thousand integer steps on the host).
 int64_t gp_ensemble_max_nodes(int32_t topology, int32_t algorithm) {
-    if (!pair_ok(topology, algorithm)) return GP_EINVAL;
-    return max_nodes(topology, algorithm);
+    return pair_ok(topology, algorithm) ? ens_max_nodes(topology, algorithm, EnsVariant{false, false}) : GP_EINVAL;
 }
 
 // gp_ensemble_create_faults' checks of the failure model.
@@ -244,6 +183,24 @@ static int faults_ok(const char* who, const gp_faults* faults) {
     }
     if (faults->reserved != 0) {
         set_err("%s: reserved must be 0 (got %lld)", who, (long long)faults->reserved);
+        return GP_EINVAL;
+    }
+    return GP_OK;
+}
+
+// gp_ensemble_create_traced's checks of the trace configuration.
+static int trace_ok(const char* who, const gp_trace_cfg* trace) {
+    if (trace->stride < 1) {
+        set_err("%s: stride must be >= 1 (got %lld)", who, (long long)trace->stride);
+        return GP_EINVAL;
+    }
+    if (trace->capacity < 0) {
+        set_err("%s: capacity must be >= 0 (got %lld)", who, (long long)trace->capacity);
+        return GP_EINVAL;
+    }
+    if (trace->reserved[0] != 0 || trace->reserved[1] != 0) {
+        set_err("%s: reserved must be 0 (got %lld, %lld)", who, (long long)trace->reserved[0],
+                (long long)trace->reserved[1]);
         return GP_EINVAL;
     }
     return GP_OK;
@@ -276,9 +233,8 @@ static int ensemble_create(const gp_config* cfg, const gp_faults* faults, const 
         set_err("gp_ensemble_create: a population of %lld has no edge", (long long)P);
         return GP_EINVAL;
     }
-    const int64_t cap = trace    ? trace_max_nodes(cfg->topology, cfg->algorithm, faults != nullptr)
-                        : faults ? faults_max_nodes(cfg->topology, cfg->algorithm)
-                                 : max_nodes(cfg->topology, cfg->algorithm);
+    const EnsVariant v{faults != nullptr, trace != nullptr};
+    const int64_t cap = ens_max_nodes(cfg->topology, cfg->algorithm, v);
     if (cfg->num_nodes > cap) {
         set_err("gp_ensemble_create: num_nodes %lld exceeds the ensemble cap %lld of this pair (one workgroup's LDS%s%s); "
                 "use gp_create", (long long)cfg->num_nodes, (long long)cap, faults ? ", failure layout" : "",
@@ -312,16 +268,15 @@ static int ensemble_create(const gp_config* cfg, const gp_faults* faults, const 
     e->g = g;
     e->nseeds = nseeds;
     e->nwords = (uint32_t)((T + 31) / 32);
+    e->v = v;
     if (faults) {
-        e->faults = true;
-        e->fp = *faults;
-        e->q_node = fault_threshold(faults->node_fail);
-        e->q_drop = fault_threshold(faults->msg_drop);
+        e->args.f.q_node = fault_threshold(faults->node_fail);
+        e->args.f.q_drop = fault_threshold(faults->msg_drop);
+        e->args.f.fail_round = faults->fail_round;
     }
     if (trace) {
-        e->traced = true;
-        e->tr.stride = trace->stride;
-        e->tr.capacity = capacity;
+        e->args.t.stride = trace->stride;
+        e->args.t.capacity = capacity;
     }
     const int rc = create(e, seeds);
     if (rc) {
@@ -342,8 +297,7 @@ int gp_ensemble_create(const gp_config* cfg, const uint64_t* seeds, int64_t nsee
 }
 
 int64_t gp_ensemble_faults_max_nodes(int32_t topology, int32_t algorithm) {
-    if (!pair_ok(topology, algorithm)) return GP_EINVAL;
-    return faults_max_nodes(topology, algorithm);
+    return pair_ok(topology, algorithm) ? ens_max_nodes(topology, algorithm, EnsVariant{true, false}) : GP_EINVAL;
 }
 
 int gp_ensemble_create_faults(const gp_config* cfg, const gp_faults* faults, const uint64_t* seeds, int64_t nseeds,
@@ -362,8 +316,7 @@ int gp_ensemble_create_faults(const gp_config* cfg, const gp_faults* faults, con
 }
 
 int64_t gp_ensemble_trace_max_nodes(int32_t topology, int32_t algorithm, int32_t faults) {
-    if (!pair_ok(topology, algorithm)) return GP_EINVAL;
-    return trace_max_nodes(topology, algorithm, faults != 0);
+    return pair_ok(topology, algorithm) ? ens_max_nodes(topology, algorithm, EnsVariant{faults != 0, true}) : GP_EINVAL;
 }
 
 int gp_ensemble_create_traced(const gp_config* cfg, const gp_faults* faults, const gp_trace_cfg* trace,
@@ -377,26 +330,14 @@ int gp_ensemble_create_traced(const gp_config* cfg, const gp_faults* faults, con
         set_err("gp_ensemble_create_traced: trace is null");
         return GP_EINVAL;
     }
-    if (trace->stride < 1) {
-        set_err("gp_ensemble_create_traced: stride must be >= 1 (got %lld)", (long long)trace->stride);
-        return GP_EINVAL;
-    }
-    if (trace->capacity < 0) {
-        set_err("gp_ensemble_create_traced: capacity must be >= 0 (got %lld)", (long long)trace->capacity);
-        return GP_EINVAL;
-    }
-    if (trace->reserved[0] != 0 || trace->reserved[1] != 0) {
-        set_err("gp_ensemble_create_traced: reserved must be 0 (got %lld, %lld)", (long long)trace->reserved[0],
-                (long long)trace->reserved[1]);
-        return GP_EINVAL;
-    }
+    if (trace_ok("gp_ensemble_create_traced", trace)) return GP_EINVAL;
     if (faults && faults_ok("gp_ensemble_create_traced", faults)) return GP_EINVAL;
     return ensemble_create(cfg, faults, trace, seeds, nseeds, out);
 }
 
 // Rows member m has recorded: a pure function of its record, no counter lives on the device.
 static int64_t trace_rows_of(const gp_ensemble* e, size_t m) {
-    return std::min(e->tr.capacity, e->rec[m].rounds / e->tr.stride);
+    return std::min(e->args.t.capacity, e->rec[m].rounds / e->args.t.stride);
 }
 
 int gp_ensemble_trace_rows(gp_ensemble* e, int64_t* rows_out) {
@@ -404,7 +345,7 @@ int gp_ensemble_trace_rows(gp_ensemble* e, int64_t* rows_out) {
         set_err("gp_ensemble_trace_rows: null argument");
         return GP_EINVAL;
     }
-    if (!e->traced) {
+    if (!e->v.trace) {
         set_err("gp_ensemble_trace_rows: the ensemble records no trace (gp_ensemble_create_traced does)");
         return GP_ESTATE;
     }
@@ -417,7 +358,7 @@ int gp_ensemble_trace_read(gp_ensemble* e, int64_t member, int64_t first, int64_
         set_err("gp_ensemble_trace_read: null handle");
         return GP_EINVAL;
     }
-    if (!e->traced) {
+    if (!e->v.trace) {
         set_err("gp_ensemble_trace_read: the ensemble records no trace (gp_ensemble_create_traced does)");
         return GP_ESTATE;
     }
@@ -437,7 +378,7 @@ int gp_ensemble_trace_read(gp_ensemble* e, int64_t member, int64_t first, int64_
         return GP_EINVAL;
     }
     HIP_TRY(hipSetDevice(e->cfg.device));
-    const gp_trace_row* src = e->tr.rows + ((size_t)member * (size_t)e->tr.capacity + (size_t)first);
+    const gp_trace_row* src = e->args.t.rows + ((size_t)member * (size_t)e->args.t.capacity + (size_t)first);
     HIP_TRY(hipMemcpyAsync(out, src, (size_t)count * sizeof(gp_trace_row), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return GP_OK;
@@ -451,10 +392,10 @@ int gp_ensemble_fault_stats(gp_ensemble* e, gp_fault_stats* out) {
     for (int64_t m = 0; m < e->nseeds; ++m) {
         gp_fault_stats& o = out[m];
         o = gp_fault_stats{0, 0, e->T, 0};
-        if (!e->faults) continue;
+        if (!e->v.faults) continue;
         const EnsFaultRec& f = e->frec[(size_t)m];
         o.doomed = f.doomed;
-        o.down = e->rec[(size_t)m].rounds >= e->fp.fail_round ? f.doomed : 0;
+        o.down = e->rec[(size_t)m].rounds >= e->args.f.fail_round ? f.doomed : 0;
         o.threshold = std::max<int64_t>(1, e->T - f.doomed);
         o.lost = f.lost;
     }
@@ -518,10 +459,10 @@ int gp_ensemble_read_state(gp_ensemble* e, int64_t member, int64_t first, int64_
     // Failure ensembles: is node first + q down at the member's round count?  D is a pure
     // function of the seed, recomputed here with the kernels' own draw.
     const gp_member& mr = e->rec[(size_t)member];
-    const bool any_down = e->faults && mr.rounds >= e->fp.fail_round;
+    const bool any_down = e->v.faults && mr.rounds >= e->args.f.fail_round;
     auto down = [&](size_t q) {
         return any_down && ens_doomed((uint32_t)mr.seed, (uint32_t)(mr.seed >> 32), (uint32_t)(first + (int64_t)q),
-                                      (uint32_t)mr.seed_node, e->q_node);
+                                      (uint32_t)mr.seed_node, e->args.f.q_node);
     };
     if (e->cfg.algorithm == GP_GOSSIP) {
         std::vector<int32_t> hc(n);

@@ -4,13 +4,15 @@
 // traffic in the round loop.  Workgroups never talk to each other; a grid larger
 // than what is resident simply queues.  DESIGN.md §9; layout: gp_ensemble.hpp.
 //
-// Included by exactly three translation units, which instantiate the templates:
-// gp_ensemble.hip with FAULTS = false (the plain kernels), gp_ensemble_faults.hip
-// with FAULTS = true (crashed nodes and lost messages, SRS v1-F) and
-// gp_ensemble_trace.hip with TRACE = true for both values of FAULTS (a row per
-// stride rounds, SRS v1-T; the other two keep TRACE = false).
-// Every line a fault adds sits under `if (FAULTS)`, every line tracing adds under
-// `if constexpr (TRACE)`, compile-time branches.
+// Included by exactly three translation units, each of which explicitly instantiates
+// ens_setup_t / ens_launch_t (declared in gp_ensemble.hpp, defined at the end of this
+// file) and with them the kernels of its variants: gp_ensemble.hip <false, false> (the
+// plain kernels), gp_ensemble_faults.hip <true, false> (crashed nodes and lost messages,
+// SRS v1-F) and gp_ensemble_trace.hip <false, true> and <true, true> (a
+// row per stride rounds, SRS v1-T).  The kernels themselves stay in the
+// anonymous namespace.  Every variant takes the same EnsArgs; every line a fault adds
+// sits under `if (FAULTS)`, every line tracing adds under `if constexpr (TRACE)`,
+// compile-time branches, so a kernel never reads the part of the arguments it has no use for.
 //
 // The rounds are SRS v1 exactly as the per-round kernels
 // and the oracle run them: same Philox draws (gp_device.hpp), push-sum folded own
@@ -27,31 +29,20 @@
 namespace gp {
 namespace {
 
-template <bool FAULTS, bool TRACE = false>
-struct EnsKernelArgs {
-    using type = EnsArgs;
-};
-template <>
-struct EnsKernelArgs<true, false> {
-    using type = EnsFaultArgs;
-};
-template <>
-struct EnsKernelArgs<false, true> {
-    using type = EnsTraceArgs;
-};
-template <>
-struct EnsKernelArgs<true, true> {
-    using type = EnsTraceFaultArgs;
-};
-// ens_model: the arguments without the trace (EnsArgs or EnsFaultArgs); ens_base: the plain ones.
-__host__ __device__ __forceinline__ const EnsArgs& ens_model(const EnsArgs& a) { return a; }
-__host__ __device__ __forceinline__ const EnsFaultArgs& ens_model(const EnsFaultArgs& f) { return f; }
-__host__ __device__ __forceinline__ const EnsArgs& ens_model(const EnsTraceArgs& t) { return t.a; }
-__host__ __device__ __forceinline__ const EnsFaultArgs& ens_model(const EnsTraceFaultArgs& t) { return t.a; }
-__host__ __device__ __forceinline__ const EnsArgs& ens_base(const EnsArgs& a) { return a; }
-__host__ __device__ __forceinline__ const EnsArgs& ens_base(const EnsFaultArgs& f) { return f.a; }
-__host__ __device__ __forceinline__ const EnsArgs& ens_base(const EnsTraceArgs& t) { return t.a; }
-__host__ __device__ __forceinline__ const EnsArgs& ens_base(const EnsTraceFaultArgs& t) { return t.a.a; }
+// Sum / maximum over the 64 lanes of a wave; every lane gets the result.
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_xor(v, off, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
 
 struct Member {
     uint32_t k0, k1;  // Philox key, wave-uniform
@@ -121,12 +112,12 @@ __device__ __forceinline__ void faults_clear(uint32_t* hdr) {
 // past P have left the caller's loop and read as 0 in the ballot.  Returns i in D.
 // This needs a workgroup of whole waves (nthr a multiple of 64, so that the first
 // lane's i is one too); ens_launch_t refuses any other launch of the failure kernels.
-__device__ __forceinline__ bool faults_draw(const EnsFaultArgs& f, const Member& M, uint32_t i, uint32_t* dm,
-                                            uint32_t* hdr) {
+__device__ __forceinline__ bool faults_draw(const EnsFaults& f, const Geom& G, const Member& M, uint32_t i,
+                                            uint32_t* dm, uint32_t* hdr) {
     const bool in = ens_doomed(M.k0, M.k1, i, M.seed_node, f.q_node);
     const uint64_t b = __ballot(in);
     if ((threadIdx.x & 63u) == 0) {
-        const uint32_t wd = i >> 5, nw = (f.a.G.P + 31u) >> 5;
+        const uint32_t wd = i >> 5, nw = (G.P + 31u) >> 5;
         dm[wd] = (uint32_t)b;
         if (wd + 1 < nw) dm[wd + 1] = (uint32_t)(b >> 32);
         if (b) atomicAdd(&hdr[2], (uint32_t)__popcll(b));
@@ -137,13 +128,13 @@ __device__ __forceinline__ bool faults_draw(const EnsFaultArgs& f, const Member&
 __device__ __forceinline__ bool faults_bit(const uint32_t* dm, uint32_t i) { return (dm[i >> 5] >> (i & 31u)) & 1u; }
 
 // T_f = max(1, T - |D|) (after the barrier that follows the redraw).
-__device__ __forceinline__ uint32_t faults_threshold(const EnsFaultArgs& f, const uint32_t* hdr) {
-    const int32_t t = (int32_t)f.a.G.T - (int32_t)hdr[2];
+__device__ __forceinline__ uint32_t faults_threshold(const Geom& G, const uint32_t* hdr) {
+    const int32_t t = (int32_t)G.T - (int32_t)hdr[2];
     return t < 1 ? 1u : (uint32_t)t;
 }
 
 // Does sender i's message of round r disappear on the way (stream S_FAULT_DROP)?
-__device__ __forceinline__ bool faults_dropped(const EnsFaultArgs& f, const Member& M, uint32_t i, uint32_t r) {
+__device__ __forceinline__ bool faults_dropped(const EnsFaults& f, const Member& M, uint32_t i, uint32_t r) {
     uint32_t x, y;
     philox2(i, r, S_FAULT_DROP, M.k0, M.k1, x, y);
     return (uint64_t)x < f.q_drop;
@@ -151,14 +142,14 @@ __device__ __forceinline__ bool faults_dropped(const EnsFaultArgs& f, const Memb
 
 // End of a launch: the threads' lost counts, one wave reduction and one LDS add per
 // wave, then a single store to the member's record.
-__device__ __forceinline__ void faults_end(const EnsFaultArgs& f, uint32_t m, uint32_t lost, uint32_t* hdr) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) lost += __shfl_xor(lost, off, 64);
+__device__ __forceinline__ void faults_end(const EnsFaults& f, uint32_t m, bool init, uint32_t lost,
+                                           uint32_t* hdr) {
+    lost = wave_sum(lost);
     if ((threadIdx.x & 63u) == 0 && lost) atomicAdd(&hdr[3], lost);
     __syncthreads();
     if (threadIdx.x == 0) {
         EnsFaultRec* fr = f.frec + m;
-        fr->lost = (f.a.init ? 0 : fr->lost) + (int64_t)hdr[3];
+        fr->lost = (init ? 0 : fr->lost) + (int64_t)hdr[3];
         fr->doomed = (int64_t)hdr[2];
     }
 }
@@ -185,21 +176,15 @@ __device__ __forceinline__ void trace_clear(const EnsTrace& t, uint32_t m, bool 
 }
 // The threads' counts into an LDS word: one wave reduction, one LDS atomic per wave.
 __device__ __forceinline__ void trace_add32(uint32_t* word, uint32_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    v = wave_sum(v);
     if ((threadIdx.x & 63u) == 0 && v) atomicAdd(word, v);
 }
 __device__ __forceinline__ void trace_add64(unsigned long long* word, uint32_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    v = wave_sum(v);
     if ((threadIdx.x & 63u) == 0 && v) atomicAdd(word, (unsigned long long)v);
 }
 __device__ __forceinline__ void trace_max64(unsigned long long* word, unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
+    v = wave_max(v);
     if ((threadIdx.x & 63u) == 0 && v) atomicMax(word, v);
 }
 // |e| of one push-sum node as its bit pattern, e = fl(fl(s / w) - mu): no floating-point
@@ -238,11 +223,9 @@ __device__ __forceinline__ void trace_end(const EnsTrace& t, uint32_t m, uint32_
 // dropped; alerts of doomed nodes are not counted.
 // TRACE (SRS v1-T): reached = nodes with c >= 1 or the seed node, bumped in phase 2; sent
 // counted per thread in phase 1 and flushed before the closing barrier of a recording round.
-template <int TOPO, bool FAULTS, bool TRACE = false>
-__global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKernelArgs<FAULTS, TRACE>::type KA) {
+template <int TOPO, bool FAULTS, bool TRACE>
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const EnsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const auto& A = ens_model(KA);
-    const EnsArgs& a = ens_base(A);
     const uint32_t P = a.G.P, tid = threadIdx.x, nthr = blockDim.x;
     uint32_t* hdr = reinterpret_cast<uint32_t*>(lds);
     unsigned char* at = lds + ENS_LDS_HDR;
@@ -272,7 +255,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKe
         if constexpr (TRACE) nreached += (i == M.seed_node || c[i] >= 1) ? 1u : 0u;
         // Imp3D random neighbour: Random().Next(0, nodes-1) -> [0, P-2] (Program.fs:259)
         if (TOPO == IMP3D) rnd[i] = (uint16_t)uniform(M.k0, M.k1, S_TOPO, i, 0, P - 1);
-        if constexpr (FAULTS) faults_draw(A, M, i, dm, hdr);
+        if constexpr (FAULTS) faults_draw(a.f, a.G, M, i, dm, hdr);
     }
     if (TOPO != FULL)
         for (uint32_t q = tid; q < a.nwords; q += nthr) {
@@ -282,22 +265,22 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKe
         }
     if (tid == 0) hdr[0] = M.alerts;
     if constexpr (TRACE)
-        if (tid == 0) trace_clear(KA.t, m, a.init, tr);
+        if (tid == 0) trace_clear(a.t, m, a.init, tr);
     __syncthreads();
-    if constexpr (FAULTS) thr = faults_threshold(A, hdr);
+    if constexpr (FAULTS) thr = faults_threshold(a.G, hdr);
     TraceClock K{};
     if constexpr (TRACE) {
         // the recount of the loaded state; phase 2 adds to it only after a later barrier
         trace_add32(&tr->reached, nreached);
-        K = trace_begin(KA.t, M);
+        K = trace_begin(a.t, M);
     }
 
     for (int64_t it = 0; it < M.left && M.alerts < thr; ++it) {
         const uint32_t r = (uint32_t)M.rounds;
         bool down_now = false;  // are the doomed nodes down in this round?  (workgroup-uniform)
-        if constexpr (FAULTS) down_now = M.rounds >= A.fail_round;
+        if constexpr (FAULTS) down_now = M.rounds >= a.f.fail_round;
         bool rec_now = false;  // does this round record a row?  (workgroup-uniform)
-        if constexpr (TRACE) rec_now = trace_records(KA.t, K, M);
+        if constexpr (TRACE) rec_now = trace_records(a.t, K, M);
         for (uint32_t i = tid; i < P; i += nthr) {
             const int32_t ci = c[i];
             if (!((i == M.seed_node || ci >= 1) && ci <= 10)) continue;  // Program.fs:85
@@ -315,7 +298,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKe
             }
             if constexpr (FAULTS) {
                 // dropped, else addressed to a down node: lost; a converged target only suppresses
-                if ((A.q_drop != 0 && faults_dropped(A, M, i, r)) || (down_now && faults_bit(dm, t))) {
+                if ((a.f.q_drop != 0 && faults_dropped(a.f, M, i, r)) || (down_now && faults_bit(dm, t))) {
                     lost += 1;
                     continue;
                 }
@@ -391,9 +374,9 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKe
         M.alerts = hdr[0];
         M.rounds += 1;
         if constexpr (TRACE) {
-            if (rec_now && tid == 0) trace_row(KA.t, m, K, M, tr);
+            if (rec_now && tid == 0) trace_row(a.t, m, K, M, tr);
             if (M.rounds == K.next_round) {
-                K.next_round += KA.t.stride;
+                K.next_round += a.t.stride;
                 K.row += 1;
             }
         }
@@ -402,8 +385,8 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKe
     for (uint32_t i = tid; i < P; i += nthr) gc[i] = c[i];
     if (TOPO != FULL)
         for (uint32_t q = tid; q < a.nwords; q += nthr) gbits[q] = bits[q];
-    if constexpr (TRACE) trace_end(KA.t, m, nsent, tr);
-    if constexpr (FAULTS) faults_end(A, m, lost, hdr);
+    if constexpr (TRACE) trace_end(a.t, m, nsent, tr);
+    if constexpr (FAULTS) faults_end(a.f, m, a.init, lost, hdr);
     member_end(a, m, M, thr);  // (thread 0 is in wave 0, which counted the injector's removals)
 }
 
@@ -421,14 +404,12 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const typename EnsKe
 // TRACE (SRS v1-T): reached = nodes with the active bit, bumped in phase B; sent counted
 // per thread in phase A; in a recording round thread 0 zeroes the err word in phase A and
 // every wave folds its nodes' |e| and its sent count in after phase B, before the closing barrier.
-template <int TOPO, int NPT, bool FAULTS, bool TRACE = false>
-__global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsKernelArgs<FAULTS, TRACE>::type KA) {
+template <int TOPO, int NPT, bool FAULTS, bool TRACE>
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const EnsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr bool LISTS = TOPO == FULL || TOPO == IMP3D;
     constexpr int LT = TOPO == LINE ? LINE : GRID3D;
     constexpr uint32_t F_DOOMED = 1u << 14;  // FAULTS: fl bit, node in D
-    const auto& A = ens_model(KA);
-    const EnsArgs& a = ens_base(A);
     const uint32_t P = a.G.P, tid = threadIdx.x, nthr = blockDim.x;
     uint32_t* hdr = reinterpret_cast<uint32_t*>(lds);
     unsigned char* at = lds + ENS_LDS_HDR;
@@ -481,28 +462,28 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsK
         if (LISTS) head[i] = ENS_NONE;
         if (TOPO == IMP3D) rnd[i] = (uint16_t)uniform(M.k0, M.k1, S_TOPO, i, 0, P - 1);
         if constexpr (FAULTS)
-            if (faults_draw(A, M, i, dm, hdr)) fl[q] |= F_DOOMED;
+            if (faults_draw(a.f, a.G, M, i, dm, hdr)) fl[q] |= F_DOOMED;
     }
     if (tid == 0) hdr[0] = M.alerts;
     if constexpr (TRACE)
-        if (tid == 0) trace_clear(KA.t, m, a.init, tr);
+        if (tid == 0) trace_clear(a.t, m, a.init, tr);
     __syncthreads();
-    if constexpr (FAULTS) thr = faults_threshold(A, hdr);
+    if constexpr (FAULTS) thr = faults_threshold(a.G, hdr);
     TraceClock K{};
     const double mu = (double)(P - 1u) * 0.5;  // TRACE: the true average
     if constexpr (TRACE) {
         // the recount of the loaded state; phase B adds to it only after a later barrier
         trace_add32(&tr->reached, nreached);
-        K = trace_begin(KA.t, M);
+        K = trace_begin(a.t, M);
     }
 
     for (int64_t it = 0; it < M.left && M.alerts < thr; ++it) {
         const uint32_t r = (uint32_t)M.rounds;
         bool down_now = false;  // are the doomed nodes down in this round?  (workgroup-uniform)
-        if constexpr (FAULTS) down_now = M.rounds >= A.fail_round;
+        if constexpr (FAULTS) down_now = M.rounds >= a.f.fail_round;
         bool rec_now = false;  // does this round record a row?  (workgroup-uniform)
         if constexpr (TRACE) {
-            rec_now = trace_records(KA.t, K, M);
+            rec_now = trace_records(a.t, K, M);
             if (rec_now && tid == 0) tr->err = 0;  // (the last row's read of it was this thread's own)
         }
 #pragma unroll
@@ -526,7 +507,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsK
                 }
                 bool gone = false;
                 if constexpr (FAULTS) {
-                    if (A.q_drop != 0) gone = faults_dropped(A, M, i, r);
+                    if (a.f.q_drop != 0) gone = faults_dropped(a.f, M, i, r);
                     if (down_now && !gone) {
                         if (TOPO != FULL && d != DIR_RANDOM) t = nbr<LT>(i, d, a.G);
                         gone = faults_bit(dm, t);
@@ -628,9 +609,9 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsK
         M.alerts = hdr[0];
         M.rounds += 1;
         if constexpr (TRACE) {
-            if (rec_now && tid == 0) trace_row(KA.t, m, K, M, tr);
+            if (rec_now && tid == 0) trace_row(a.t, m, K, M, tr);
             if (M.rounds == K.next_round) {
-                K.next_round += KA.t.stride;
+                K.next_round += a.t.stride;
                 K.row += 1;
             }
         }
@@ -644,8 +625,8 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const typename EnsK
         gw[i] = w[q];
         gf[i] = (uint8_t)(fl[q] & 15u);
     }
-    if constexpr (TRACE) trace_end(KA.t, m, nsent, tr);
-    if constexpr (FAULTS) faults_end(A, m, lost, hdr);
+    if constexpr (TRACE) trace_end(a.t, m, nsent, tr);
+    if constexpr (FAULTS) faults_end(a.f, m, a.init, lost, hdr);
     member_end(a, m, M, thr);
 }
 
@@ -661,7 +642,7 @@ inline uint32_t ens_threads(int alg, uint32_t P) {
     return t > (uint32_t)ENS_THREADS ? (uint32_t)ENS_THREADS : t;
 }
 
-template <int TOPO, bool FAULTS, bool TRACE = false>
+template <int TOPO, bool FAULTS, bool TRACE>
 const void* ps_kernel(int npt) {
     switch (npt) {
         case 1: return reinterpret_cast<const void*>(&k_ens_pushsum<TOPO, 1, FAULTS, TRACE>);
@@ -673,7 +654,7 @@ const void* ps_kernel(int npt) {
 }
 static_assert(ENS_NPT_MAX == 8, "ps_kernel lists the slot counts");
 
-template <bool FAULTS, bool TRACE = false>
+template <bool FAULTS, bool TRACE>
 const void* ens_kernel(int topo, int alg, uint32_t P) {
     if (alg == GOSSIP) {
         switch (topo) {
@@ -694,27 +675,28 @@ const void* ens_kernel(int topo, int alg, uint32_t P) {
     }
 }
 
-template <bool FAULTS, bool TRACE = false>
+}  // namespace
+
+template <bool FAULTS, bool TRACE>
 hipError_t ens_setup_t(int topo, int alg, uint32_t P) {
+    constexpr EnsVariant v{FAULTS, TRACE};
     const void* k = ens_kernel<FAULTS, TRACE>(topo, alg, P);
-    if (!k || P > ens_max_population(topo, alg, FAULTS, TRACE)) return hipErrorInvalidValue;  // a missing kernel is an error
-    return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)ens_lds_bytes(topo, alg, P, FAULTS, TRACE));
+    if (!k || P > ens_max_population(topo, alg, v)) return hipErrorInvalidValue;  // a missing kernel is an error
+    return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ens_lds_bytes(topo, alg, P, v));
 }
 
-template <bool FAULTS, bool TRACE = false>
-hipError_t ens_launch_t(int topo, int alg, const typename EnsKernelArgs<FAULTS, TRACE>::type& A, uint32_t nblocks,
-                        hipStream_t st) {
-    const uint32_t P = ens_base(A).G.P;
+template <bool FAULTS, bool TRACE>
+hipError_t ens_launch_t(int topo, int alg, const EnsArgs& a, uint32_t nblocks, hipStream_t st) {
+    constexpr EnsVariant v{FAULTS, TRACE};
+    const uint32_t P = a.G.P;
     const void* k = ens_kernel<FAULTS, TRACE>(topo, alg, P);
-    if (!k || P > ens_max_population(topo, alg, FAULTS, TRACE)) return hipErrorInvalidValue;
+    if (!k || P > ens_max_population(topo, alg, v)) return hipErrorInvalidValue;
     const uint32_t threads = ens_threads(alg, P);
     // faults_draw stores whole waves' bitmap words; the trace reduces over whole waves
     if ((FAULTS || TRACE) && threads % 64u != 0) return hipErrorInvalidValue;
-    typename EnsKernelArgs<FAULTS, TRACE>::type copy = A;
+    EnsArgs copy = a;
     void* args[] = {&copy};
-    return hipLaunchKernel(k, dim3(nblocks), dim3(threads), args, ens_lds_bytes(topo, alg, P, FAULTS, TRACE), st);
+    return hipLaunchKernel(k, dim3(nblocks), dim3(threads), args, ens_lds_bytes(topo, alg, P, v), st);
 }
 
-}  // namespace
 }  // namespace gp

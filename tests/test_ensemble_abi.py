@@ -44,6 +44,23 @@ def test_max_nodes_covers_the_report_range(topo, alg):
     assert L.lib().gp_ensemble_max_nodes(topo, alg) >= 1000
 
 
+# num_nodes caps of the four layouts (plain, trace, failure, failure + trace), computed from the LDS
+# layout of gp_ensemble.hpp on the CPU.  Only full push-sum is LDS-bound in every layout.
+CAPS = {(L.GP_LINE, L.GP_GOSSIP): 8191, (L.GP_LINE, L.GP_PUSHSUM): 8191, (L.GP_FULL, L.GP_GOSSIP): 8191,
+        (L.GP_3D, L.GP_GOSSIP): 8000, (L.GP_3D, L.GP_PUSHSUM): 8000, (L.GP_IMP3D, L.GP_GOSSIP): 8000,
+        (L.GP_IMP3D, L.GP_PUSHSUM): 5832, (L.GP_FULL, L.GP_PUSHSUM): (6979, 6978, 6940, 6939)}
+
+
+@pytest.mark.parametrize("topo,alg", PAIRS)
+def test_the_caps_of_every_layout_are_what_they_were(topo, alg):
+    lib = L.lib()
+    want = CAPS[topo, alg]
+    want = want if isinstance(want, tuple) else (want,) * 4
+    got = (lib.gp_ensemble_max_nodes(topo, alg), lib.gp_ensemble_trace_max_nodes(topo, alg, 0),
+           lib.gp_ensemble_faults_max_nodes(topo, alg), lib.gp_ensemble_trace_max_nodes(topo, alg, 1))
+    assert got == want
+
+
 def test_max_nodes_refuses_unknown_pair():
     lib = L.lib()
     assert lib.gp_ensemble_max_nodes(4, L.GP_GOSSIP) == GP_EINVAL
