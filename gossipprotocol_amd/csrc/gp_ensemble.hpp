@@ -1,86 +1,22 @@
 // gp_ensemble.hpp -- ensemble runs (gp_ensemble.hip): one workgroup simulates one
 // whole small network in LDS, a grid of workgroups runs many seeds at once.
-// This header is the variant descriptor, the LDS layout (and with it the population cap
-// per pair and variant), the kernel arguments and the host launch interface; DESIGN.md §9.
+// This header is the kernel arguments and the host launch interface; the variant descriptor
+// and the launch shape (LDS layout, population caps, slots, threads) are gp_ensemble_shape.hpp;
+// DESIGN.md §9.
 #pragma once
 
 #include <stdint.h>
 
 #include "../../include/gossip_hip.h"
 #include "gp_device.hpp"
+#include "gp_ensemble_shape.hpp"
 
 namespace gp {
 
-constexpr int ENS_THREADS = 1024;            // largest workgroup
-constexpr int ENS_NPT_MAX = 8;               // push-sum: node slots a thread keeps in registers
-constexpr uint32_t ENS_LDS_MAX = 150 * 1024; // dynamic LDS a member may ask for (a CU has 160 KiB)
-constexpr uint32_t ENS_LDS_HDR = 16;         // [0] cumulative alerts, [1] injector live count;
-                                             // failure kernels: [2] |D|, [3] messages lost in this launch
-constexpr uint32_t ENS_NONE = 0xFFFFu;       // end of a receiver's message list (node ids are < 0xFFFF)
-
-constexpr uint32_t ens_up8(uint32_t b) { return (b + 7u) & ~7u; }
-
-// Which kernels run an ensemble: with the failure model, recording a trace.
-struct EnsVariant {
-    bool faults, trace;
-};
-
-// LDS image of one member, arrays in this order, each padded to 8 bytes:
-//   gossip   : c int32[P], inc int32[P], rnd u16[P] (Imp3D), live bitmap u32[ceil(T/32)] (not full)
-//   push-sum : hs f64[P], hw f64[P] (the halves a sender offers this round), head u32[P] + next u16[P]
-//              (full, Imp3D: per-receiver list of this round's random-edge senders), rnd u16[P] (Imp3D),
-//              dir u8[P] (not full)
-// The per-node (s, w, flags) of push-sum live in registers (ENS_NPT_MAX slots per thread).
-// The failure kernels (SRS v1-F, gp_ensemble_faults.hip) append
-//   doomed bitmap u32[ceil(P/32)]: bit i set iff node i is in D
-// to either image, redrawn from the seed at the start of every launch.
-// The traced kernels (SRS v1-T, gp_ensemble_trace.hip) append after that
-//   trace block, ENS_LDS_TRACE bytes (EnsTraceLds): the words a row is made of
-constexpr uint32_t ENS_LDS_TRACE = 32;
-constexpr uint32_t ens_lds_bytes(int topo, int alg, uint32_t P, EnsVariant v) {
-    uint32_t b = ENS_LDS_HDR;
-    if (alg == GOSSIP) {
-        b += ens_up8(4 * P) * 2;
-        if (topo == IMP3D) b += ens_up8(2 * P);
-        if (topo != FULL) b += ens_up8(4 * ((P + 31) / 32));
-    } else {
-        b += 8 * P * 2;
-        if (topo == FULL || topo == IMP3D) b += ens_up8(4 * P) + ens_up8(2 * P);
-        if (topo == IMP3D) b += ens_up8(2 * P);
-        if (topo != FULL) b += ens_up8(P);
-    }
-    if (v.faults) b += ens_up8(4 * ((P + 31) / 32));
-    if (v.trace) b += ENS_LDS_TRACE;
-    return b;
-}
-
-// Largest population a member may have: the LDS image fits and every node has a
-// thread slot.  A compile-time function of the layout above.
-constexpr uint32_t ens_max_population(int topo, int alg, EnsVariant v) {
-    uint32_t P = (uint32_t)ENS_THREADS * ENS_NPT_MAX;
-    while (P > 2 && ens_lds_bytes(topo, alg, P, v) > ENS_LDS_MAX) --P;
-    return P;
-}
-// Every variant of every pair covers the report's range.
-constexpr bool ens_covers_report_range() {
-    for (int faults = 0; faults < 2; ++faults)
-        for (int trace = 0; trace < 2; ++trace)
-            for (int topo = LINE; topo <= IMP3D; ++topo)
-                for (int alg = GOSSIP; alg <= PUSHSUM; ++alg)
-                    if (ens_max_population(topo, alg, EnsVariant{faults != 0, trace != 0}) < 1001) return false;
-    return true;
-}
-static_assert(ens_covers_report_range(), "report range");
-static_assert((uint32_t)ENS_THREADS * ENS_NPT_MAX < ENS_NONE, "node ids must fit the 16-bit list links");
-
-// Largest num_nodes: line / full P = n + 1; 3D / Imp3D the largest whole cube.
-constexpr int64_t ens_max_nodes(int topo, int alg, EnsVariant v) {
-    const uint32_t P = ens_max_population(topo, alg, v);
-    if (topo == LINE || topo == FULL) return (int64_t)P - 1;
-    uint32_t g = 1;
-    while ((g + 1) * (g + 1) * (g + 1) <= P) ++g;
-    return (int64_t)g * g * g;
-}
+// The launch shape -- LDS layout, population caps, node slots and workgroup size -- is host-clean
+// and lives in gp_ensemble_shape.hpp, written over the public enums:
+static_assert(LINE == GP_LINE && FULL == GP_FULL && GRID3D == GP_3D && IMP3D == GP_IMP3D, "topology enums");
+static_assert(GOSSIP == GP_GOSSIP && PUSHSUM == GP_PUSHSUM, "algorithm enums");
 
 // Failure model (SRS v1-F): Philox streams and the per-member record
 // that persists between launches beside gp_member (whose `converged` carries the

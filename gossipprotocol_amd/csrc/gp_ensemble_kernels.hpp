@@ -2,7 +2,7 @@
 // (member idx[b], seed rec[m].seed) with its node state in LDS and registers, a
 // workgroup barrier between the phases of a round, no launch per round and no HBM
 // traffic in the round loop.  Workgroups never talk to each other; a grid larger
-// than what is resident simply queues.  DESIGN.md §9; layout: gp_ensemble.hpp.
+// than what is resident simply queues.  DESIGN.md §9; layout and launch shape: gp_ensemble_shape.hpp.
 //
 // Included by exactly three translation units, each of which explicitly instantiates
 // ens_setup_t / ens_launch_t (declared in gp_ensemble.hpp, defined at the end of this
@@ -628,18 +628,6 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const EnsArgs a) {
     if constexpr (TRACE) trace_end(a.t, m, nsent, tr);
     if constexpr (FAULTS) faults_end(a.f, m, a.init, lost, hdr);
     member_end(a, m, M, thr);
-}
-
-inline int ens_npt(uint32_t P) {
-    int npt = 1;
-    while ((uint32_t)npt * ENS_THREADS < P) npt *= 2;
-    return npt;
-}
-
-inline uint32_t ens_threads(int alg, uint32_t P) {
-    const uint32_t per = alg == PUSHSUM ? (P + ens_npt(P) - 1) / ens_npt(P) : P;
-    const uint32_t t = (per + 63u) & ~63u;
-    return t > (uint32_t)ENS_THREADS ? (uint32_t)ENS_THREADS : t;
 }
 
 template <int TOPO, bool FAULTS, bool TRACE>
