@@ -648,6 +648,23 @@ int64_t or_active_count(const or_sim* s) {
     return a;
 }
 
+/* Ids still on the injector's list: prefix sums of the Fenwick tree the picks are
+ * drawn from (fen_kth), so the counts are those of the list the run uses. */
+static int64_t fen_prefix(const or_sim* s, int64_t n) {
+    int64_t sum = 0;
+    for (int64_t i = n; i > 0; i -= i & -i) sum += s->fen[i];
+    return sum;
+}
+
+int64_t or_injector_listed(const or_sim* s, int64_t first, int64_t count) {
+    if (!s->fen || first < 0 || count < 0) return -1;
+    int64_t lo = first < s->T ? first : s->T;
+    int64_t hi = count < s->T - lo ? lo + count : s->T;
+    return fen_prefix(s, hi) - fen_prefix(s, lo);
+}
+
+int64_t or_injector_live(const or_sim* s) { return s->fen ? s->live : -1; }
+
 int or_read_state(const or_sim* s, int64_t first, int64_t count, int32_t* c,
                   double* sv, double* wv, uint8_t* flags) {
     if (first < 0 || count < 0 || first + count > s->P) return -1;

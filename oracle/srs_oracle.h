@@ -67,6 +67,12 @@ int or_neighbors(const or_sim* s, int64_t i, int64_t* out);
 int or_read_state(const or_sim* s, int64_t first, int64_t count, int32_t* c,
                   double* sv, double* wv, uint8_t* flags);
 
+/* The gossip injector's list L (Program.fs:147-148; line / 3D / Imp3D): how many ids of
+ * [first, first+count) are still listed (the range is clipped to [0, T)), and |L|.
+ * Both return -1 when the case has no injector (full topology, push-sum). */
+int64_t or_injector_listed(const or_sim* s, int64_t first, int64_t count);
+int64_t or_injector_live(const or_sim* s);
+
 /* Push-sum round `round` for the distinct receivers ids[0..nids) from a full
  * round-start state (all P nodes: s, w, flags as or_read_state) -- the check of
  * the product's round at populations the whole-network oracle cannot run.

@@ -34,9 +34,11 @@ def lib():
         L.or_step.restype = i64
         L.or_step.argtypes = [vp, i64, C.POINTER(i64)]
         for f in ("or_rounds_done", "or_alerts_total", "or_population", "or_threshold",
-                  "or_seed_node", "or_active_count", "or_activate_all"):
+                  "or_seed_node", "or_active_count", "or_activate_all", "or_injector_live"):
             getattr(L, f).restype = i64
             getattr(L, f).argtypes = [vp]
+        L.or_injector_listed.restype = i64
+        L.or_injector_listed.argtypes = [vp, i64, i64]
         L.or_neighbors.restype = i32
         L.or_neighbors.argtypes = [vp, i64, C.POINTER(i64)]
         L.or_read_state.restype = i32
@@ -137,6 +139,15 @@ class Oracle:
         """bench.py cpu_baseline timing only: every push-sum node active (skips the
         activation pre-roll; not an SRS v1 transition)."""
         return lib().or_activate_all(self._h)
+
+    def injector_listed(self, first, count):
+        """Ids of [first, first + count) still on the gossip injector's list; -1 without injector."""
+        return lib().or_injector_listed(self._h, first, count)
+
+    @property
+    def injector_live(self):
+        """|L| of the gossip injector; -1 without injector."""
+        return lib().or_injector_live(self._h)
 
     def neighbors(self, i):
         d = lib().or_neighbors(self._h, i, None)

@@ -39,15 +39,10 @@ Full gossip (k_full_gossip_send / _recv, and the k_fullm_* kernels on three rank
 (uniform(.., 1)) and at populations around its 256-thread blocks and 2^16.
 
 Injector, two chunks (inj_find / inj_remove, 65536 ids per chunk): g = 41 has T = 68921, so the
-second chunk holds 3385 ids.  NOT covered here, and nowhere else in the suite: a long two-chunk
-run.  Gossip at g = 41 stalls at 0.83 T alerts within 500 rounds (3D 56 987, Imp3D 57 662 of
-68 921, seed 3); from there only the injector's one pick per round moves it (57 138 / 57 809 at
-round 3000), and 0.9 T -- the share from which picks mostly remove converged ids from both
-chunks -- is reached only in round 59 001..60 000 (3D) / 58 001..59 000 (Imp3D) of the 97 286 /
-97 560 the whole run takes: 50 to 60 s of oracle time per topology before the first compared
-round that meets it, as long as the run that drains the second chunk to empty (56 s).  Both are
-too long for this suite and remain unpinned; the two-chunk list is compared over its first 400
-rounds only (test_gpu_parity.py, 125 000 nodes).
+second chunk holds 3385 ids.  The long two-chunk run -- g = 41 and the line n = 65537 to
+convergence, about 10^5 rounds in which the second chunk drains to empty -- is a minute of oracle
+time per topology, too long to run here: tests/test_gpu_injector_drain.py compares it with the
+oracle's recorded runs (tests/golden/runs_injector.json).
 """
 import functools
 from collections import Counter, namedtuple
