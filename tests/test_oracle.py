@@ -196,3 +196,52 @@ def test_activate_all_is_a_steady_state_round():
     assert (st1["w"] != 1.0).sum() > P // 2  # every node halved and/or received
     orc.close()
     assert Oracle(1000, "line", "gossip", 1).activate_all() == -1
+
+
+# Seeds whose high word is set: the Philox key is (seed & 0xFFFFFFFF, seed >> 32), and every other
+# seed of the suite but the ensembles' is below 2^32 (key word 1 = 0).
+WIDE_SEEDS = (2**63 + 3,              # k0 = 3, k1 = 0x80000000
+              1 << 32,                # k0 = 0, k1 = 1
+              2**64 - 1,              # both words all ones: both key-schedule additions carry in round 1
+              0x9E3779B9_00000005)    # k0 = 5, k1 = the k0 increment
+WIDE_PAIRS = [(n, topo, alg) for topo, n in (("line", 60), ("full", 60), ("3D", 64), ("Imp3D", 64))
+              for alg in ("gossip", "push-sum")]
+
+
+@pytest.mark.parametrize("seed", WIDE_SEEDS, ids=hex)
+@pytest.mark.parametrize("n,topo,alg", WIDE_PAIRS)
+def test_c_oracle_vs_python_oracle_wide_seeds(n, topo, alg, seed):
+    """Both oracles on seeds with the high word set, all 8 topology x algorithm pairs, 200 rounds or to
+    convergence: equal seed node, per-round alerts and full state.  (All four seeds of the issue hold
+    for every shape; none had to be replaced.)"""
+    o, p = Oracle(n, topo, alg, seed), srs_py.PySim(n, topo, alg, seed)
+    assert o.seed_node == p.seed_node
+    assert o.step(200) == p.step(200)
+    st = o.state()
+    if alg == "gossip":
+        assert list(st["c"]) == p.c
+    else:
+        assert list(st["s"]) == p.s and list(st["w"]) == p.w
+    assert list(st["flags"]) == p.flags()
+
+
+def differs_within(n, topo, alg, a, b, rounds=50):
+    """The oracle's runs of seeds a and b differ in the seed node, or in the first `rounds` rounds'
+    alerts or the state after them."""
+    oa, ob = Oracle(n, topo, alg, a), Oracle(n, topo, alg, b)
+    if oa.seed_node != ob.seed_node or oa.step(rounds) != ob.step(rounds):
+        return True
+    sa, sb = oa.state(), ob.state()
+    return any(not np.array_equal(sa[k], sb[k]) for k in ("c", "s", "w", "flags"))
+
+
+@pytest.mark.parametrize("n,topo,alg", WIDE_PAIRS)
+def test_high_seed_word_changes_the_run(n, topo, alg):
+    """s = 5 and s + 2^32 share key word 0 and differ in key word 1 alone: the runs differ, so a run
+    that dropped the high word cannot match the oracle by coincidence.  The same for every wide seed
+    against its low word alone (k1 = 0) and against its low word twice (k1 = k0)."""
+    assert differs_within(n, topo, alg, 5, 5 + 2**32)
+    for seed in WIDE_SEEDS:
+        k0 = seed & 0xFFFFFFFF
+        assert differs_within(n, topo, alg, seed, k0)
+        assert (k0 << 32 | k0) == seed or differs_within(n, topo, alg, seed, k0 << 32 | k0)
