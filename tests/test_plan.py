@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from tests import multirank_emu as emu
+from tests.test_gpu_lattice_rank_edges import GRID_E, LINE_SHAPES, demonstrate, shape
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 XMAXH = 8
@@ -90,6 +91,33 @@ def test_full_topology_plan(plan, W, n):
                 q.append(("pair_cap", s_hi - s_lo, bounds[b + 1] - bounds[b], P))
                 want.append([emu.full_capacity(s_hi - s_lo, bounds[b + 1] - bounds[b], P)])
     assert plan(q) == want
+
+
+# the shapes of tests/test_gpu_lattice_rank_edges.py: (topology, size, W), size = P for the line, g for 3D
+LATTICE_RANK_EDGE_SHAPES = [("line", P, W) for W, P in LINE_SHAPES] + [("3D", g, W) for g, W in GRID_E]
+
+
+@pytest.mark.parametrize("topo,size,W", LATTICE_RANK_EDGE_SHAPES, ids=lambda v: str(v))
+def test_lattice_rank_edge_shapes(plan, topo, size, W):
+    """Slab bounds, halo and tiles per slab of the line and 3D edge cases: the header's against the
+    restatements the cases derive their cut positions from."""
+    sh = shape(topo, size, W)
+    bounds, halo = emu.slab_bounds(sh.P, sh.g, topo, W)
+    q = [("bounds", sh.P, sh.g, W, 0 if topo == "line" else 2)]
+    q += [("tiles_for", lo, hi - lo) for lo, hi in zip(bounds, bounds[1:])]
+    got = plan(q)
+    assert got[0] == [0, halo] + bounds and sh.bounds == bounds
+    assert [t for (t,) in got[1:]] == sh.tiles == [emu.tiles_for(lo, hi - lo) for lo, hi in zip(bounds, bounds[1:])]
+
+
+@pytest.mark.parametrize("alg", ["push-sum", "gossip"])
+@pytest.mark.parametrize("topo,size,W", LATTICE_RANK_EDGE_SHAPES, ids=lambda v: str(v))
+def test_lattice_rank_edge_demonstrations(topo, size, W, alg):
+    """The CPU demonstration of every case of tests/test_gpu_lattice_rank_edges.py with its committed
+    seed and round count (oracle and Philox draws only): a send up and a send down across every cut
+    within the executed rounds, the cut nodes active (gossip: reached) at the last checkpoint."""
+    t = demonstrate(topo, size, W, alg)
+    assert sorted(t.states)[-1] == t.R == len(t.alerts)
 
 
 def test_bounds_rejections_and_cuts(plan):
