@@ -6,7 +6,7 @@ message delivery of gossip and push-sum on line / full / 3D / Imp3D
 topologies plus the convergence check, as HIP kernels for gfx950 behind the
 C-ABI in include/gossip_hip.h.  See DESIGN.md.
 """
-from .sim import (ALGORITHMS, TOPOLOGIES, Ensemble, Faults, Simulation, Trace, ensemble_max_nodes,  # noqa: F401
-                  parse_algorithm, parse_topology, resolve, run)
+from .sim import (ALGORITHMS, TOPOLOGIES, Ensemble, Faults, Simulation, Trace, Values,  # noqa: F401
+                  default_mean, ensemble_max_nodes, parse_algorithm, parse_topology, resolve, run)
 
 __version__ = "1.0.0"

@@ -74,6 +74,12 @@ class GpTraceCfg(C.Structure):
     _fields_ = [("stride", C.c_int64), ("capacity", C.c_int64), ("reserved", C.c_int64 * 2)]
 
 
+class GpValues(C.Structure):
+    """Values and weights every member of an ensemble starts from (gp_values)."""
+    _fields_ = [("x", C.POINTER(C.c_double)), ("w", C.POINTER(C.c_double)), ("count", C.c_int64),
+                ("mean", C.c_double), ("reserved", C.c_int64)]
+
+
 class GpSummary(C.Structure):
     """What a run computed, reduced on the device (gp_summary)."""
     _fields_ = [("first", C.c_int64), ("count", C.c_int64), ("population", C.c_int64), ("rounds", C.c_int64),
@@ -97,7 +103,7 @@ class GpSummary(C.Structure):
 
     @property
     def rms_error(self):
-        """Root mean square over the covered nodes of e = s / w - (P - 1) / 2."""
+        """Root mean square over the covered nodes of e = s / w - mu (mu: the handle's mean)."""
         return (self.sum_sqerr[0] / self.count) ** 0.5 if self.count else 0.0
 
     def merge(self, other):
@@ -147,6 +153,10 @@ SIGNATURES = [
     ("gp_summary_take", _i32, [_vp, C.c_double, _i32, C.POINTER(GpSummary)]),
     ("gp_summary_merge", _i32, [C.POINTER(GpSummary), C.POINTER(GpSummary), C.POINTER(GpSummary)]),
     ("gp_ensemble_summary", _i32, [_vp, C.c_double, C.POINTER(GpSummary)]),
+    ("gp_set_values", _i32, [_vp, _i64, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("gp_set_mean", _i32, [_vp, C.c_double]),
+    ("gp_ensemble_create_values", _i32, [C.POINTER(GpConfig), C.POINTER(GpValues), C.POINTER(GpFaults),
+                                         C.POINTER(GpTraceCfg), C.POINTER(C.c_uint64), _i64, C.POINTER(_vp)]),
 ]
 
 _libs = {}

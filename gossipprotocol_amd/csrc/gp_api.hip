@@ -253,6 +253,14 @@ int64_t gp_step(gp_sim* s, int64_t nrounds, int64_t* alerts_out) {
         set_err("hipSetDevice failed");
         return GP_EHIP;
     }
+    if (s->vstage.bytes) values_stage_free(s->vstage);  // (values are the initial state: no use for the staging from here on)
+    if (s->values_dirty) {  // gp_set_values after create's round-0 exchange: halo planes and lists again (SRS v1-V)
+        s->values_dirty = false;
+        if (s->rounds_done == 0) {
+            const int rc = exchange(s, 0);
+            if (rc) return rc;
+        }
+    }
     int64_t executed = 0;
     while (executed < nrounds && !s->done) {
         int64_t batch = std::min<int64_t>(nrounds - executed, BATCH);
@@ -552,6 +560,7 @@ void gp_destroy(gp_sim* s) {
     }
     if (s->comm) (void)ncclCommDestroy(s->comm);
     for (void* p : s->allocs) (void)hipFree(p);
+    values_stage_free(s->vstage);
     if (s->host_ctl) (void)hipHostFree(s->host_ctl);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     if (s->xstream) (void)hipStreamDestroy(s->xstream);

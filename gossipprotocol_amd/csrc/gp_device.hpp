@@ -140,8 +140,10 @@ GP_HD uint32_t uniform(uint32_t k0, uint32_t k1, uint32_t stream, uint32_t node,
 //   N = s2 w - s w2 (b = fma(s2, w, -RN(s w2)), m = RN(w w2)):  |b| > 2^-18 m
 // implies |s2/w2 - s/w| = |N| / (w w2) > 2^-20 + 2^-33 >= 1e-10 (1 + 2^-52) +
 // 2^-53 (|s2/w2| + |s/w|), i.e. even after rounding both quotients (each off by
-// at most 2^-53 of a ratio < 2^32: every ratio is a weighted mean of node ids,
-// ids < 2^32) and their difference, the exact test says "moved".  Margins: the
+// at most 2^-53 of a ratio < 2^32 -- the premise: every ratio s / w a run forms is
+// a weighted mean of the initial x_i / w_i, each below 2^32; node ids with weight 1
+// by default, and what gp_set_values admits, x_i * 2^-32 < w_i, SRS v1-V) and
+// their difference, the exact test says "moved".  Margins: the
 // error of b is at most 2^-53 (|N| + s w2 (1 + 2^-53)) <= 2^-53 |N| + 2^-21 w w2,
 // that of m 2^-53 m; the products stay normal (the m and s w2 guards), and s, w
 // are >= 0 / > 0.  Everything else -- slow ratio changes, the converging tail --

@@ -49,7 +49,8 @@ struct EnsTraceLds {
     unsigned long long sent;  // messages sent, all launches so far (threads flush into it before a row is taken)
     unsigned long long err;   // push-sum: largest |e| bit pattern of the recording round
     uint32_t reached;         // recounted at launch start, then kept incrementally
-    uint32_t pad[3];
+    uint32_t pad;
+    double mu;                // push-sum: what err is measured against (EnsArgs::mu), read where a row's errors are taken
 };
 static_assert(sizeof(EnsTraceLds) == ENS_LDS_TRACE, "trace block");
 struct EnsTraceRec {
@@ -80,6 +81,11 @@ struct EnsArgs {
     int64_t max_rounds;  // cap on a member's total rounds
     EnsFaults f;
     EnsTrace t;
+    // push-sum, SRS v1-V (gp_ensemble_create_values): the initial (s, w) of every member, P doubles
+    // each on the device; x0 null: s = id, w = 1; w0 null: every weight 1.  Read by the set-up launch only.
+    const double* x0;
+    const double* w0;
+    double mu;  // TRACE: what err_max is measured against; (P - 1) / 2 unless values were given
 };
 
 // The launch interface of one variant, defined in gp_ensemble_kernels.hpp and instantiated by

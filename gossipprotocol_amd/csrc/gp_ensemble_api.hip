@@ -70,6 +70,7 @@ struct gp_ensemble {
     std::vector<uint32_t> running; // unfinished members, in member order
     SumAcc* d_sum = nullptr;       // gp_ensemble_summary: one record per member, allocated at the first call
     std::vector<EnsFaultRec> frec; // v.faults: host copy of args.f.frec, refreshed after every launch
+    double mean = 0.0;             // mu of the summaries and the trace: (P - 1) / 2 unless values were given (SRS v1-V)
 };
 
 namespace {
@@ -109,7 +110,7 @@ int launch(gp_ensemble* e, int64_t nrounds, bool init) {
     return GP_OK;
 }
 
-int create(gp_ensemble* e, const uint64_t* seeds) {
+int create(gp_ensemble* e, const uint64_t* seeds, const gp_values* values) {
     const int topo = e->cfg.topology, alg = e->cfg.algorithm;
     const size_t n = (size_t)e->nseeds, P = (size_t)e->P;
     HIP_TRY(hipSetDevice(e->cfg.device));
@@ -136,6 +137,28 @@ int create(gp_ensemble* e, const uint64_t* seeds) {
         if (!rc) rc = ens_alloc(e, &a.fl, n * P);
     }
     if (rc) return rc;
+    if (values) {  // SRS v1-V: checked on the device (gp_values.hip), then kept for the set-up launch
+        double *x0 = nullptr, *w0 = nullptr;
+        if ((rc = ens_alloc(e, &x0, P)) || (values->w && (rc = ens_alloc(e, &w0, P)))) return rc;
+        struct Sink : ValSink {  // the staged chunk, once it has passed the check, into the two arrays
+            double *x0, *w0;
+            int write(const void* staged, bool weighted, int64_t c0, int64_t c1, hipStream_t st) override {
+                HIP_TRY(launch_values_split(staged, weighted, (uint32_t)(c1 - c0), x0 + c0, weighted ? w0 + c0 : nullptr,
+                                            (int)ENS_CUS, st));
+                return GP_OK;
+            }
+        } sink;
+        sink.x0 = x0;
+        sink.w0 = w0;
+        ValStage stage;
+        rc = values_stream(stage, e->stream, (int)ENS_CUS, "gp_ensemble_create_values", values->x, values->w, (int64_t)P,
+                           0, &sink);
+        values_stage_free(stage);
+        if (rc) return rc;
+        a.x0 = x0;
+        a.w0 = w0;
+    }
+    a.mu = e->mean;
     a.idx = e->d_idx;
     a.G = Geom{};
     a.G.P = (uint32_t)e->P;
@@ -208,8 +231,9 @@ static int trace_ok(const char* who, const gp_trace_cfg* trace) {
 
 // gp_ensemble_create, gp_ensemble_create_faults (faults != null) and gp_ensemble_create_traced
 // (trace != null), their own arguments already checked.
-static int ensemble_create(const gp_config* cfg, const gp_faults* faults, const gp_trace_cfg* trace,
-                           const uint64_t* seeds, int64_t nseeds, gp_ensemble** out) {
+// values != null: gp_ensemble_create_values, its own fields but count already checked.
+static int ensemble_create(const gp_config* cfg, const gp_values* values, const gp_faults* faults,
+                           const gp_trace_cfg* trace, const uint64_t* seeds, int64_t nseeds, gp_ensemble** out) {
     if (!seeds) {
         set_err("gp_ensemble_create: seeds is null");
         return GP_EINVAL;
@@ -231,6 +255,10 @@ static int ensemble_create(const gp_config* cfg, const gp_faults* faults, const 
     if (gp_resolve(cfg->num_nodes, cfg->topology, &P, &T, &g)) return GP_EINVAL;
     if (P < 2) {
         set_err("gp_ensemble_create: a population of %lld has no edge", (long long)P);
+        return GP_EINVAL;
+    }
+    if (values && values->count != P) {
+        set_err("gp_ensemble_create_values: count %lld is not the population %lld", (long long)values->count, (long long)P);
         return GP_EINVAL;
     }
     const EnsVariant v{faults != nullptr, trace != nullptr};
@@ -269,6 +297,7 @@ static int ensemble_create(const gp_config* cfg, const gp_faults* faults, const 
     e->nseeds = nseeds;
     e->nwords = (uint32_t)((T + 31) / 32);
     e->v = v;
+    e->mean = values ? values->mean : (double)(P - 1) * 0.5;
     if (faults) {
         e->args.f.q_node = fault_threshold(faults->node_fail);
         e->args.f.q_drop = fault_threshold(faults->msg_drop);
@@ -278,7 +307,7 @@ static int ensemble_create(const gp_config* cfg, const gp_faults* faults, const 
         e->args.t.stride = trace->stride;
         e->args.t.capacity = capacity;
     }
-    const int rc = create(e, seeds);
+    const int rc = create(e, seeds, values);
     if (rc) {
         gp_ensemble_destroy(e);  // (hipFree does not touch the error message)
         return rc;
@@ -293,7 +322,7 @@ int gp_ensemble_create(const gp_config* cfg, const uint64_t* seeds, int64_t nsee
         return GP_EINVAL;
     }
     *out = nullptr;
-    return ensemble_create(cfg, nullptr, nullptr, seeds, nseeds, out);
+    return ensemble_create(cfg, nullptr, nullptr, nullptr, seeds, nseeds, out);
 }
 
 int64_t gp_ensemble_faults_max_nodes(int32_t topology, int32_t algorithm) {
@@ -312,7 +341,7 @@ int gp_ensemble_create_faults(const gp_config* cfg, const gp_faults* faults, con
         return GP_EINVAL;
     }
     if (faults_ok("gp_ensemble_create_faults", faults)) return GP_EINVAL;
-    return ensemble_create(cfg, faults, nullptr, seeds, nseeds, out);
+    return ensemble_create(cfg, nullptr, faults, nullptr, seeds, nseeds, out);
 }
 
 int64_t gp_ensemble_trace_max_nodes(int32_t topology, int32_t algorithm, int32_t faults) {
@@ -332,7 +361,40 @@ int gp_ensemble_create_traced(const gp_config* cfg, const gp_faults* faults, con
     }
     if (trace_ok("gp_ensemble_create_traced", trace)) return GP_EINVAL;
     if (faults && faults_ok("gp_ensemble_create_traced", faults)) return GP_EINVAL;
-    return ensemble_create(cfg, faults, trace, seeds, nseeds, out);
+    return ensemble_create(cfg, nullptr, faults, trace, seeds, nseeds, out);
+}
+
+int gp_ensemble_create_values(const gp_config* cfg, const gp_values* values, const gp_faults* faults,
+                              const gp_trace_cfg* trace, const uint64_t* seeds, int64_t nseeds, gp_ensemble** out) {
+    const char* who = "gp_ensemble_create_values";
+    if (!cfg || !out) {
+        set_err("%s: null argument", who);
+        return GP_EINVAL;
+    }
+    *out = nullptr;
+    if (!values) {
+        set_err("%s: values is null", who);
+        return GP_EINVAL;
+    }
+    if (!values->x) {
+        set_err("%s: values.x is null", who);
+        return GP_EINVAL;
+    }
+    if (values->reserved != 0) {
+        set_err("%s: reserved must be 0 (got %lld)", who, (long long)values->reserved);
+        return GP_EINVAL;
+    }
+    if (!mean_ok(values->mean)) {
+        set_err("%s: mean must be finite, >= 0 and < 2^32 (got %g)", who, values->mean);
+        return GP_EINVAL;
+    }
+    if (cfg->algorithm == GP_GOSSIP) {
+        set_err("%s: gossip has no values (cfg.algorithm is gossip)", who);
+        return GP_EINVAL;
+    }
+    if (trace && trace_ok(who, trace)) return GP_EINVAL;
+    if (faults && faults_ok(who, faults)) return GP_EINVAL;
+    return ensemble_create(cfg, values, faults, trace, seeds, nseeds, out);
 }
 
 // Rows member m has recorded: a pure function of its record, no counter lives on the device.
@@ -516,7 +578,7 @@ int gp_ensemble_summary(gp_ensemble* e, double tol, gp_summary* out) {
     a.fl = e->args.fl;
     a.rec = e->args.rec;
     a.P = (uint32_t)e->P;
-    a.mu = (double)(e->P - 1) * 0.5;
+    a.mu = e->mean;
     a.tol = tol;
     a.out = e->d_sum;
     const int alg = e->cfg.algorithm == GP_PUSHSUM ? PUSHSUM : GOSSIP;

@@ -169,10 +169,11 @@ __device__ __forceinline__ bool trace_records(const EnsTrace& t, const TraceCloc
     return M.rounds + 1 == K.next_round && K.row < t.capacity;
 }
 // Thread 0, before the barrier that ends the set-up: sent continues from the member's record.
-__device__ __forceinline__ void trace_clear(const EnsTrace& t, uint32_t m, bool init, EnsTraceLds* tr) {
+__device__ __forceinline__ void trace_clear(const EnsTrace& t, uint32_t m, bool init, double mu, EnsTraceLds* tr) {
     tr->sent = init ? 0ull : (unsigned long long)t.trec[m].sent;
     tr->err = 0;
     tr->reached = 0;
+    tr->mu = mu;
 }
 // The threads' counts into an LDS word: one wave reduction, one LDS atomic per wave.
 __device__ __forceinline__ void trace_add32(uint32_t* word, uint32_t v) {
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const EnsArgs a) {
         }
     if (tid == 0) hdr[0] = M.alerts;
     if constexpr (TRACE)
-        if (tid == 0) trace_clear(a.t, m, a.init, tr);
+        if (tid == 0) trace_clear(a.t, m, a.init, a.mu, tr);
     __syncthreads();
     if constexpr (FAULTS) thr = faults_threshold(a.G, hdr);
     TraceClock K{};
@@ -464,13 +465,21 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const EnsArgs a) {
         if constexpr (FAULTS)
             if (faults_draw(a.f, a.G, M, i, dm, hdr)) fl[q] |= F_DOOMED;
     }
+    if (a.init && a.x0) {  // SRS v1-V: sum = x_i, weight = omega_i where the caller gave them (set-up launch only)
+#pragma unroll
+        for (int q = 0; q < NPT; ++q) {
+            const uint32_t i = tid + q * nthr;
+            if (i >= P) continue;
+            s[q] = a.x0[i];
+            if (a.w0) w[q] = a.w0[i];
+        }
+    }
     if (tid == 0) hdr[0] = M.alerts;
     if constexpr (TRACE)
-        if (tid == 0) trace_clear(a.t, m, a.init, tr);
+        if (tid == 0) trace_clear(a.t, m, a.init, a.mu, tr);
     __syncthreads();
     if constexpr (FAULTS) thr = faults_threshold(a.G, hdr);
     TraceClock K{};
-    const double mu = (double)(P - 1u) * 0.5;  // TRACE: the true average
     if constexpr (TRACE) {
         // the recount of the loaded state; phase B adds to it only after a later barrier
         trace_add32(&tr->reached, nreached);
@@ -593,6 +602,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const EnsArgs a) {
             if (rec_now) {
                 // all P nodes, down ones included (their s, w are frozen); the division is paid here only
                 unsigned long long e = 0;
+                const double mu = tr->mu;  // the handle's mean
 #pragma unroll
                 for (int q = 0; q < NPT; ++q) {
                     if (tid + q * nthr >= P) continue;

@@ -33,8 +33,9 @@
 
 #include "gp_xchg.hpp"
 
-using namespace gp;
 #pragma GCC visibility push(hidden)
+#include "gp_values.hpp"
+using namespace gp;
 
 // The calling thread's gp_last_error() message: one slot per thread for all units (gp_api.hip).
 extern thread_local std::string g_err;
@@ -165,6 +166,12 @@ struct gp_sim {
     // gp_summary_take (gp_summary.hip): partial records and gather buffer, allocated at the first call
     void* sum_scratch = nullptr;
     size_t sum_scratch_bytes = 0;
+    // SRS v1-V (gp_values.hip): mu, the value the summaries' error fields are measured against --
+    // (P - 1) / 2 unless gp_set_mean changed it; the staging of gp_set_values; values_dirty: values
+    // were set on a handle whose round-0 exchange has run (gp_step repeats it before round 0)
+    double mean = 0.0;
+    ValStage vstage;
+    bool values_dirty = false;
 };
 #pragma GCC visibility push(hidden)
 

@@ -376,6 +376,7 @@ int create_common(const gp_config* cfg, int mode, int world, int rank, const uin
     s->P = P;
     s->T = T;
     s->g = g;
+    s->mean = (double)(P - 1) * 0.5;
     s->mode = mode;
     s->world = world;
     s->rank = rank;

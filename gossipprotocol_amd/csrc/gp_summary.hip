@@ -407,7 +407,7 @@ int gp_summary_take(gp_sim* s, double tol, int32_t scope, gp_summary* out) {
         }
         a.n = S.nloc;
         a.seed_node = S.seed_node;
-        a.mu = (double)(s->P - 1) * 0.5;
+        a.mu = s->mean;
         a.tol = tol;
         a.part = part + at;
         HIP_TRY(summary_launch(alg, a, blocks[q], s->stream));

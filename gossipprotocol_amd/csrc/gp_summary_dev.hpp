@@ -33,7 +33,7 @@ struct SummaryArgs {
     uint32_t n;          // owned nodes
     uint32_t id0;        // node id of array index 0
     uint32_t seed_node;
-    double mu, tol;      // (P - 1) / 2; tolerance on |e|
+    double mu, tol;      // the handle's mean ((P - 1) / 2 unless values were set); tolerance on |e|
     SumAcc* part;        // one record per workgroup
 };
 

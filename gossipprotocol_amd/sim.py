@@ -11,6 +11,7 @@ tests.  Every call goes to libgossip_hip.so; there is no CPU path here.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -35,6 +36,18 @@ def resolve(num_nodes: int, topology: str):
     P, T, g = C.c_int64(), C.c_int64(), C.c_int64()
     L.check(L.lib().gp_resolve(num_nodes, parse_topology(topology), C.byref(P), C.byref(T), C.byref(g)))
     return P.value, T.value, g.value
+
+
+def default_mean(x, w=None) -> float:
+    """The default mu of a value run: math.fsum(x) / math.fsum(w), or math.fsum(x) / len(x) without
+    weights -- the correctly rounded sums, one division."""
+    return math.fsum(x) / (math.fsum(w) if w is not None else len(x))
+
+
+def _f64(a):
+    """A contiguous float64 copy-or-view of `a` and its ctypes pointer."""
+    arr = np.ascontiguousarray(a, np.float64)
+    return arr, arr.ctypes.data_as(C.POINTER(C.c_double))
 
 
 class Simulation:
@@ -119,6 +132,30 @@ class Simulation:
 
     def sync(self):
         self._chk(self._L.gp_sync(self._h))
+
+    # -- caller-supplied data (SRS v1-V) -------------
+    def set_values(self, x, w=None, first: int = 0, mean: float | None = None):
+        """Push-sum over your data: node first + k starts from s = x[k], w = w[k] (all 1 without
+        `w`) instead of s = id, w = 1 (gp_set_values).  Before the first round only; may be called
+        repeatedly to load a large network in chunks, each call all or nothing.  Entries must be
+        admissible (include/gossip_hip.h: non-negative, finite, weights in [2^-32, 2^32], x = 0 or
+        >= 2^-64, x / w < 2^32); shift negative data first.  `mean` sets mu, what the summary's
+        error fields are measured against; mean=None with first == 0 and len(x) == P computes
+        :func:`default_mean`, otherwise the mean is left alone (see :meth:`set_mean`)."""
+        xa, xp = _f64(x)
+        wa, wp = (None, None) if w is None else _f64(w)
+        if wa is not None and len(wa) != len(xa):
+            raise ValueError(f"{len(xa)} values but {len(wa)} weights")
+        self._chk(self._L.gp_set_values(self._h, first, len(xa), xp, wp))
+        if mean is None and first == 0 and len(xa) == self.population:
+            mean = default_mean(xa.tolist(), None if wa is None else wa.tolist())
+        if mean is not None:
+            self.set_mean(mean)
+
+    def set_mean(self, mu: float):
+        """mu of the summaries (gp_set_mean): finite, >= 0, < 2^32.  Every rank of a multi-process
+        run sets the same value."""
+        self._chk(self._L.gp_set_mean(self._h, float(mu)))
 
     # -- inspection ------------------------------------------------------
     def info(self) -> L.GpInfo:
@@ -225,6 +262,23 @@ class Trace:
         return f"Trace(stride={self.stride}, capacity={self.capacity})"
 
 
+class Values:
+    """The data every member of an :class:`Ensemble` starts from (gp_values; SRS v1-V, DESIGN.md
+    section 13): node i holds s = x[i], w = w[i] (all 1 without `w`); ``mean`` is mu, what the
+    summaries' and the trace's errors are measured against (default: :func:`default_mean`)."""
+
+    def __init__(self, x, w=None, mean: float | None = None):
+        self.x = np.ascontiguousarray(x, np.float64)
+        self.w = None if w is None else np.ascontiguousarray(w, np.float64)
+        if self.w is not None and len(self.w) != len(self.x):
+            raise ValueError(f"{len(self.x)} values but {len(self.w)} weights")
+        self.mean = float(default_mean(self.x.tolist(), None if self.w is None else self.w.tolist())
+                          if mean is None else mean)
+
+    def __repr__(self):
+        return f"Values({len(self.x)} values, {'weighted' if self.w is not None else 'unweighted'}, mean={self.mean!r})"
+
+
 # one row of a trace (gp_trace_row)
 TRACE_DTYPE = np.dtype([("round", "<i8"), ("reached", "<u4"), ("alerts", "<u4"), ("sent", "<u8"), ("err_max", "<f8")])
 
@@ -236,10 +290,12 @@ class Ensemble:
     is bit-identical to ``Simulation(num_nodes, topology, algorithm, seed)``.  With
     ``faults=Faults(...)`` nodes crash and messages get lost (gp_ensemble_create_faults); with
     ``trace=Trace(...)`` every member records its spread curve inside the kernel
-    (gp_ensemble_create_traced), read with :meth:`trace`."""
+    (gp_ensemble_create_traced), read with :meth:`trace`; with ``values=Values(...)`` every
+    push-sum member averages your data instead of the node ids (gp_ensemble_create_values).  The
+    three compose."""
 
     def __init__(self, num_nodes: int, topology: str, algorithm: str, seeds, max_rounds: int, device: int = 0,
-                 faults: "Faults | None" = None, trace: "Trace | None" = None):
+                 faults: "Faults | None" = None, trace: "Trace | None" = None, values: "Values | None" = None):
         self._L = L.lib()
         self.seeds = [int(s) for s in seeds]
         cfg = L.GpConfig()
@@ -255,8 +311,16 @@ class Ensemble:
         h = C.c_void_p()
         self.faults, self.tracing = faults, trace
         f = None if faults is None else L.GpFaults(faults.node_fail, faults.msg_drop, faults.fail_round, 0)
-        if trace is not None:
-            t = L.GpTraceCfg(trace.stride, trace.capacity)
+        self.values = values
+        t = None if trace is None else L.GpTraceCfg(trace.stride, trace.capacity)
+        if values is not None:
+            dp = C.POINTER(C.c_double)
+            v = L.GpValues(values.x.ctypes.data_as(dp), None if values.w is None else values.w.ctypes.data_as(dp),
+                           len(values.x), values.mean, 0)
+            L.check(self._L.gp_ensemble_create_values(C.byref(cfg), C.byref(v), None if f is None else C.byref(f),
+                                                      None if t is None else C.byref(t), arr, len(self.seeds),
+                                                      C.byref(h)), self._L)
+        elif trace is not None:
             L.check(self._L.gp_ensemble_create_traced(C.byref(cfg), None if f is None else C.byref(f), C.byref(t), arr,
                                                       len(self.seeds), C.byref(h)), self._L)
         elif faults is None:

@@ -264,7 +264,8 @@ typedef struct gp_trace_row {   /* 32 bytes, blittable */
                           round start; push-sum: active at round start; under the failure model: and not
                           down in that round.  Suppressed, dropped and lost messages count (they were sent);
                           the gossip injector's picks do not. */
-    double   err_max;  /* push-sum: max over all P nodes of |fl(fl(s/w) - mu)|, mu = (P-1)/2, exactly as
+    double   err_max;  /* push-sum: max over all P nodes of |fl(fl(s/w) - mu)|, mu = the handle's mean,
+                          (P - 1) / 2 unless values were set, exactly as
                           gp_summary.err_max defines the term, taken as the largest 64-bit pattern with the
                           sign bit cleared; a pattern above +inf's reads as the quiet NaN 0x7FF8000000000000.
                           gossip: 0.0 */
@@ -307,7 +308,8 @@ typedef struct gp_summary {      /* blittable, fixed layout (304 bytes) */
     int64_t cnt_hist[4];         /* nodes whose stability count (flag bits 2-3) is 0..3 */
     double  est_min, est_max;    /* min / max over the nodes of the estimate fl(s / w) */
     double  w_min, w_max;        /* min / max weight */
-    double  err_max;             /* max |e|, e = fl(fl(s / w) - mu), mu = (P - 1) / 2 (the true average) */
+    double  err_max;             /* max |e|, e = fl(fl(s / w) - mu), mu = the handle's mean, (P - 1) / 2 unless
+                                    values were set */
     int64_t err_max_node;        /* lowest node id attaining err_max */
     int64_t within_tol;          /* nodes with |e| <= tol */
     double  tol;                 /* the tolerance the summary was taken with */
@@ -331,6 +333,55 @@ int gp_summary_merge(const gp_summary* a, const gp_summary* b, gp_summary* out);
 /* One summary per ensemble member into out (nseeds records, each with first = 0 and
  * count = P, rounds = the member's), in one launch. */
 int gp_ensemble_summary(gp_ensemble* e, double tol, gp_summary* out);
+
+/* ---- Push-sum over caller-supplied values and weights: SRS v1-V ---
+ * Push-sum aggregates data that lives on the nodes; without these calls every run averages
+ * s_i = i, w_i = 1.  SRS v1-V is SRS v1 with the push-sum initial state s_i = x_i, w_i = omega_i
+ * (count = 1, only the seed node active); the stop rule, the Philox streams, the fold order and
+ * the ratio test are v1's.  Gossip has no values: these calls refuse a gossip configuration with
+ * GP_EINVAL.  A handle that never sets values, and an ensemble made by the other entry points,
+ * is bit-identical to what it was.
+ *
+ * Admissible input -- every entry is checked (on the device), and a call with an inadmissible
+ * one returns GP_EINVAL, changes nothing, and names the lowest offending node id and its rule in
+ * gp_last_error():
+ *   - x_i and omega_i are finite with the sign bit clear (-0.0 is refused);
+ *   - omega_i in [2^-32, 2^32]; a null weight pointer means all weights are 1;
+ *   - x_i = 0, or x_i >= 2^-64;
+ *   - x_i * 2^-32 < omega_i, so that every ratio s / w a run forms stays below 2^32.
+ * Negative data is out of scope: the caller shifts it.
+ *
+ * mu, the value err_max, err_max_node, within_tol and sum_sqerr of the summaries and err_max of
+ * the trace rows are measured against, is an input of a value run, not something the library
+ * derives: finite, >= 0 and < 2^32. */
+typedef struct gp_values {      /* blittable */
+    const double* x;            /* count values */
+    const double* w;            /* count weights, or NULL: all 1 */
+    int64_t count;
+    double mean;                /* mu */
+    int64_t reserved;           /* 0 */
+} gp_values;
+
+/* Overwrites the initial (s, w) of node ids [first, first + count).  Push-sum handles only
+ * (else GP_EINVAL), and only while the handle has run no round (else GP_ESTATE).  The range must
+ * lie inside the ids the handle owns: all P for a single-GPU or virtual-rank handle, the slab
+ * for a gp_create_rank handle.  May be called any number of times, so a large network can be
+ * loaded in chunks (the arrays are streamed through a bounded pinned buffer; a call of at most
+ * 2^20 nodes is uploaded once, a longer one twice); each call is all or nothing.  Flags, count,
+ * active bit and seed node stay as they are.  On gp_create_rank handles, if any rank sets values
+ * every rank calls gp_set_values at least once (count 0 will do) before the first gp_step. */
+int gp_set_values(gp_sim* sim, int64_t first, int64_t count, const double* x, const double* w);
+/* Sets mu (any round).  On gp_create_rank handles every rank sets the same value:
+ * gp_summary_merge cannot check it, the 304-byte record does not carry mu. */
+int gp_set_mean(gp_sim* sim, double mean);
+
+/* gp_ensemble_create / _create_faults / _create_traced (faults and trace may be NULL) where every
+ * member starts from the same P values.  Every check of those applies, against the same
+ * gp_ensemble_*_max_nodes; in addition values must be non-null with x non-null, count == P,
+ * reserved == 0, an admissible mean and admissible entries, and cfg must be push-sum. */
+int gp_ensemble_create_values(const gp_config* cfg, const gp_values* values, const gp_faults* faults,
+                              const gp_trace_cfg* trace, const uint64_t* seeds, int64_t nseeds,
+                              gp_ensemble** out);
 
 #ifdef __cplusplus
 }
