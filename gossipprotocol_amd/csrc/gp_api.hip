@@ -71,7 +71,7 @@ static double alg_bytes(const gp_sim* s) {
     //   delivery count read (a byte since round 4; was 4 B), its zeroing where non-zero
     //   and the senders' atomic increments (~1/7 of nodes each, a 4-B word atomic) ->
     //   15 + 5/7 (4-B counts: 18 + 8/7; several ranks: the remote 7/8 of the increments
-    //   arrive through k_unpack instead);
+    //   arrive as bits, counted by k_apply_bits instead);
     //   tile kernel: in-list 8
     if (S.topo == IMP3D) return S.rq[0] ? (S.rq8 ? 15.0 + 5.0 / 7.0 : 18.0 + 8.0 / 7.0) : 18.0;
     if (S.topo != FULL) return 10.0;

@@ -17,8 +17,8 @@
 // (the pointers depend on the round through its parity only), in the order they are issued:
 //   1. the halo node bytes, lower neighbour then upper;
 //   2. with them the halo (s, w): compacted (hsend / hrecv, setup_halo) or the full planes;
-//   3. per peer the payload: its bitmap chunk; or its list's header words, then messages; or
-//      its slot / bin buffer.
+//   3. per peer the payload of the run's exchange kind (kplan.xkind): its bitmap chunk; or its
+//      list's header words, then messages; or its slot / bin buffer.
 // The k-th send of rank a to rank d is the k-th receive d posts from a: RCCL matches them
 // by that order, and in-process ranks check it (run_transfers).
 void build_transfers(gp_sim* s) {
@@ -52,17 +52,24 @@ void build_transfers(gp_sim* s) {
                     if (p == r) continue;
                     std::vector<Xfer>& v = sl.xplan[b][h];
                     const size_t i = (size_t)h * W + p;
-                    if (sl.bits) {  // the bitmap chunks, each way
+                    switch (s->kplan.xkind) {
+                    case XKind::None:  // (line / 3D: the halo planes are all that travels)
+                        break;
+                    case XKind::Bits:  // the bitmap chunks, each way
                         add(v, true, p, S.sbits + sl.bl.bo[p] / 32, (size_t)(sl.bl.bn[p] + 31) / 32 * 4);
                         add(v, false, p, sl.rbits_in + sl.bl.ro[p] / 32, (size_t)(sl.bl.rn[p] + 31) / 32 * 4);
-                    } else if (sl.lists) {  // header words, then messages, each way
+                        break;
+                    case XKind::Lists:  // header words, then messages, each way
                         add(v, true, p, sl.xsend + sl.xl.lhdr[i], (size_t)s->list_nw[((size_t)r * NH + h) * W + p] * 16);
                         add(v, true, p, sl.xsend + sl.xl.lval[i], (size_t)sl.xl.cap_out[i] * 16);
                         add(v, false, p, xr + sl.xl.rhdr[i], (size_t)s->list_nw[((size_t)p * NH + h) * W + r] * 16);
                         add(v, false, p, xr + sl.xl.rval[i], (size_t)sl.xl.cap_in[i] * 16);
-                    } else if (!sl.xl.sbytes.empty()) {  // slot buffers (gossip) / coarse bins (full push-sum)
+                        break;
+                    case XKind::Slots:     // slot buffers (gossip)
+                    case XKind::FullBins:  // coarse bins (full push-sum)
                         add(v, true, p, sl.xsend + sl.xl.soff[i], sl.xl.sbytes[i]);
                         add(v, false, p, sl.xrecv + sl.xl.roff[i], sl.xl.rbytes[i]);
+                        break;
                     }
                 }
         }
@@ -76,7 +83,6 @@ XPeer xpeer(uint8_t* buf, size_t off, uint32_t cap) {
     uint8_t* b = buf + off;
     p.cnt = reinterpret_cast<uint32_t*>(b);
     p.slots = reinterpret_cast<uint32_t*>(b + XBUF_SLOTS_OFF);
-    p.vals = reinterpret_cast<double2*>(b + xbuf_vals_off(cap));
     p.cap = cap;
     return p;
 }
@@ -334,31 +340,34 @@ int launch_round_full_multi(gp_sim* s, uint32_t r, hipEvent_t e0, hipEvent_t e1)
 }
 
 // Halo refresh + Imp3D random-edge exchange for round `rn`, whose state the
-// previous round kernel has just written to buffers rn & 1.  Push-sum moves the
-// random-edge messages as sender-ordered lists (k_list_pack: header words + compacted
-// messages, read in place by the next round kernel -- no unpack) in two regions
-// (s->xhalves): region 0 is packed and handed to the exchange stream, whose transfer
-// (with the halo planes) overlaps region 1's packing.  Gossip packs {slot} or {count}
-// entries and unpacks them (k_pack / k_unpack).  Events order the streams, so every
-// rank issues its RCCL groups in one order (region 0, region 1), before the finalize
-// all-reduce on the compute stream.  exchange() = exchange_open, exchange_region for every
-// region (halo planes in region 0's group), exchange_close; launch_round_regions runs the same
-// pieces region by region behind the round kernel's launches (halo planes in the last group).
+// previous round kernel has just written to buffers rn & 1.  What the random edges need is the
+// run's exchange kind (kplan.xkind).  Lists (push-sum): k_list_pack writes header words +
+// compacted messages, read in place by the next round kernel -- no unpack -- in s->xhalves
+// regions: a region is packed and handed to the exchange stream, whose transfer overlaps the
+// next region's packing.  Slots (gossip, tile kernel): k_pack writes {slot} entries, k_unpack
+// tags the in-edges they name.  Bits (gossip, column kernel): the round kernel has set the
+// bits; k_apply_bits counts the received ones.  None (line / 3D): halo planes only.  Events
+// order the streams, so every rank issues its RCCL groups in one order (region 0, 1, ...),
+// before the finalize all-reduce on the compute stream.  exchange() = exchange_open,
+// exchange_region for every region (halo planes in region 0's group), exchange_close;
+// launch_round_regions runs the same pieces region by region behind the round kernel's
+// launches (halo planes in the last group).
 struct XchgCtx {
+    XKind kind;
     int W, b, NH;
-    bool push, imp, lists, bits;
+    bool push;
     hipStream_t xs;
     size_t HS;
     XchgCtx(const gp_sim* s, uint32_t rn) {
+        kind = s->kplan.xkind;
         W = s->world;
         b = rn & 1;
         push = s->cfg.algorithm == GP_PUSHSUM;
-        imp = s->cfg.topology == GP_IMP3D;
-        NH = imp ? s->xhalves : 1;
+        // Lists: the slab's regions; else 1 -- gossip has one region, line / 3D never set xhalves, and
+        // the full topology (xhalves 2 for push-sum) never comes here: exchange() returns before
+        NH = s->xhalves;
         xs = NH > 1 && s->xstream ? s->xstream : s->stream;
         HS = s->halo_slots;  // push-sum: the halo planes' (s, w) compacted (setup_halo)
-        lists = imp && push && s->slab[0].lists;
-        bits = imp && s->slab[0].bits;
     }
 };
 
@@ -372,123 +381,125 @@ int exchange_open(gp_sim* s, uint32_t rn, hipStream_t cs) {
     return s->mode == MODE_VIRTUAL ? run_transfers(s, x.b, 0, true, false, cs) : GP_OK;
 }
 
+// Lists: header words + compacted messages of a slab's region h (k_list_pack).
+int pack_lists(Slab& sl, const XchgCtx& x, int h, hipStream_t cs) {
+    const DevState& S = sl.S;
+    const int W = x.W;
+    HIP_TRY(hipMemsetAsync(sl.xcnt + (size_t)h * W, 0, sizeof(uint32_t) * W, cs));
+    ListPackArgs la{};
+    la.nbn = S.nb[x.b];
+    la.swn = S.sw[x.b];
+    la.xdr = sl.xdr;
+    la.lwt = sl.lwt;
+    la.gw = sl.gw;
+    la.lo = S.lo;
+    la.nloc = S.nloc;
+    la.base = S.base;
+    la.t0 = sl.tb[h];
+    la.t1 = h + 1 == x.NH ? sl.nt : sl.tb[h + 1];
+    la.W = W;
+    la.me = sl.rank;
+    for (int d = 0; d < W; ++d) {
+        if (d == sl.rank) continue;
+        const size_t i = (size_t)h * W + d;
+        la.peer[d].hdr = reinterpret_cast<XHdr*>(sl.xsend + sl.xl.lhdr[i]);
+        la.peer[d].vals = reinterpret_cast<double2*>(sl.xsend + sl.xl.lval[i]);
+        la.peer[d].cnt = sl.xcnt + i;
+        la.peer[d].cap = sl.xl.cap_out[i];
+        la.peer[d].vbase = sl.xl.vbase[i];
+    }
+    la.overflow = sl.overflow;
+    HIP_TRY(launch_list_pack(la, cs));
+    return GP_OK;
+}
+
+// Slots: the {slot} entries of a slab's region h, per destination (k_pack).
+int pack_slots(Slab& sl, const XchgCtx& x, int h, hipStream_t cs) {
+    const DevState& S = sl.S;
+    const int W = x.W;
+    ZeroArgs z{};
+    PackArgs pa{};
+    pa.nbn = S.nb[x.b];
+    pa.pos = sl.pos;
+    pa.xdst = sl.xdst;
+    pa.lo = S.lo;
+    pa.nloc = S.nloc;
+    xregion(S.lo, S.nloc, /* lists */ false, sl.tb, x.NH, h, pa.s_lo, pa.s_hi);
+    pa.base = S.base;
+    pa.W = W;
+    pa.me = sl.rank;
+    for (int p = 0; p < W; ++p) {
+        const size_t i = (size_t)h * W + p;
+        pa.peer[p] = xpeer(sl.xsend, sl.xl.soff[i], sl.xl.cap_out[i]);
+        z.cnt[p] = pa.peer[p].cnt;
+    }
+    z.n = W;
+    pa.overflow = sl.overflow;
+    HIP_TRY(launch_zero_counts(z, cs));
+    HIP_TRY(launch_pack(pa, cs));
+    return GP_OK;
+}
+
+// Slots: region h's received entries tag the in-edges they name with round rn (k_unpack).
+int unpack_slots(Slab& sl, const XchgCtx& x, int h, uint32_t rn, hipStream_t st) {
+    UnpackArgs ua{};
+    ua.rtag = sl.S.rtag;
+    ua.nedges = sl.nedges;
+    ua.W = x.W;
+    ua.me = sl.rank;
+    for (int p = 0; p < x.W; ++p) {
+        const size_t i = (size_t)h * x.W + p;
+        ua.peer[p] = xpeer(sl.xrecv, sl.xl.roff[i], sl.xl.cap_in[i]);
+    }
+    ua.overflow = sl.overflow;
+    HIP_TRY(launch_unpack(ua, rn, st));
+    return GP_OK;
+}
+
 // Region h of round rn's random-edge exchange: packed on the compute stream, then handed to the
 // exchange stream (one RCCL group per region; the halo planes travel in region hg's group).
 int exchange_region(gp_sim* s, uint32_t rn, int h, int hg, hipStream_t cs) {
     const XchgCtx x(s, rn);
-    const int W = x.W, b = x.b, NH = x.NH;
-    const bool push = x.push, imp = x.imp, lists = x.lists, bits = x.bits;
-    const hipStream_t xs = x.xs;
     int rc;
-    if (imp && !bits) {  // (bitmaps: set by the round kernel itself)
-        for (Slab& sl : s->slab) {
-            DevState& S = sl.S;
-            if (lists) {  // header words + compacted messages of region h (k_list_pack)
-                HIP_TRY(hipMemsetAsync(sl.xcnt + (size_t)h * W, 0, sizeof(uint32_t) * W, cs));
-                ListPackArgs la{};
-                la.nbn = S.nb[b];
-                la.swn = S.sw[b];
-                la.xdr = sl.xdr;
-                la.lwt = sl.lwt;
-                la.gw = sl.gw;
-                la.lo = S.lo;
-                la.nloc = S.nloc;
-                la.base = S.base;
-                la.t0 = sl.tb[h];
-                la.t1 = h + 1 == NH ? sl.nt : sl.tb[h + 1];
-                la.W = W;
-                la.me = sl.rank;
-                for (int d = 0; d < W; ++d) {
-                    if (d == sl.rank) continue;
-                    const size_t i = (size_t)h * W + d;
-                    la.peer[d].hdr = reinterpret_cast<XHdr*>(sl.xsend + sl.xl.lhdr[i]);
-                    la.peer[d].vals = reinterpret_cast<double2*>(sl.xsend + sl.xl.lval[i]);
-                    la.peer[d].cnt = sl.xcnt + i;
-                    la.peer[d].cap = sl.xl.cap_out[i];
-                    la.peer[d].vbase = sl.xl.vbase[i];
-                }
-                la.overflow = sl.overflow;
-                HIP_TRY(launch_list_pack(la, cs));
-                continue;
-            }
-            ZeroArgs z{};
-            PackArgs pa{};
-            pa.nbn = S.nb[b];
-            pa.swn = push ? S.sw[b] : nullptr;
-            pa.rnd = S.rnd;
-            pa.pos = sl.pos;
-            pa.xdst = sl.xdst;
-            pa.lo = S.lo;
-            pa.nloc = S.nloc;
-            xregion(S.lo, S.nloc, sl.lists, sl.tb, NH, h, pa.s_lo, pa.s_hi);
-            pa.base = S.base;
-            pa.W = W;
-            pa.me = sl.rank;
-            pa.push = push ? 1 : 0;
-            pa.counts = col_gossip_counts(S) ? 1 : 0;
-            for (int w = 0; w <= W; ++w) pa.bounds[w] = s->bounds[w];
-            for (int p = 0; p < W; ++p) {
-                const size_t i = (size_t)h * W + p;
-                pa.peer[p] = xpeer(sl.xsend, sl.xl.soff[i], sl.xl.cap_out[i]);
-                z.cnt[p] = pa.peer[p].cnt;
-            }
-            z.n = W;
-            pa.overflow = sl.overflow;
-            HIP_TRY(launch_zero_counts(z, cs));
-            HIP_TRY(launch_pack(pa, s->grid, cs));
-        }
+    for (Slab& sl : s->slab) {
+        if (x.kind == XKind::Lists && (rc = pack_lists(sl, x, h, cs))) return rc;
+        if (x.kind == XKind::Slots && (rc = pack_slots(sl, x, h, cs))) return rc;
+        // (Bits: set by the round kernel itself)
     }
-    if (xs != s->stream) {
+    if (x.xs != s->stream) {
         HIP_TRY(hipEventRecord(s->ev_send[h], cs));
-        HIP_TRY(hipStreamWaitEvent(xs, s->ev_send[h], 0));
+        HIP_TRY(hipStreamWaitEvent(x.xs, s->ev_send[h], 0));
     }
     // (in-process ranks have copied the halo planes on the packs' stream: exchange_open)
-    if ((rc = run_transfers(s, b, h, s->mode == MODE_RCCL && h == hg, true, xs))) return rc;
-    if (xs != s->stream) HIP_TRY(hipEventRecord(s->ev_xfer[h], xs));
+    if ((rc = run_transfers(s, x.b, h, s->mode == MODE_RCCL && h == hg, true, x.xs))) return rc;
+    if (x.xs != s->stream) HIP_TRY(hipEventRecord(s->ev_xfer[h], x.xs));
     return GP_OK;
 }
 
 // After the last region: received bitmaps applied / entries unpacked, halo planes expanded.
 int exchange_close(gp_sim* s, uint32_t rn) {
     const XchgCtx x(s, rn);
-    const int W = x.W, b = x.b, NH = x.NH;
-    const bool push = x.push, imp = x.imp, lists = x.lists, bits = x.bits;
-    const hipStream_t xs = x.xs;
     int rc;
-    if (bits) {
-        if (xs != s->stream) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_xfer[NH - 1], 0));
+    // (the exchange stream runs the regions' transfers in order: after the last, all are here)
+    if (x.xs != s->stream) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_xfer[x.NH - 1], 0));
+    switch (x.kind) {
+    case XKind::Bits:
         for (Slab& sl : s->slab) {
             // one rumour per received bit at its target, counted for round rn; then the send
             // bitmap is cleared for the next round kernel
             HIP_TRY(launch_apply_bits(sl.rbits_in, sl.bl.nbits_in / 32, sl.tgt, sl.S.rq[rn & 1], sl.S.rq8, s->stream));
             if (sl.bl.nbits_out) HIP_TRY(hipMemsetAsync(sl.S.sbits, 0, (size_t)sl.bl.nbits_out / 8, s->stream));
         }
-    } else if (imp && !lists) {
-        for (int h = 0; h < NH; ++h) {
-            if (xs != s->stream) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_xfer[h], 0));
-            for (Slab& sl : s->slab) {
-                UnpackArgs ua{};
-                ua.rtag = sl.S.rtag;
-                ua.rmsg = sl.S.rmsg;
-                ua.rq = col_gossip_counts(sl.S) ? sl.S.rq[rn & 1] : nullptr;  // next round's deliveries
-                ua.rq8 = sl.S.rq8;
-                ua.nedges = ua.rq ? sl.S.nloc : sl.nedges;
-                ua.W = W;
-                ua.me = sl.rank;
-                ua.push = push ? 1 : 0;
-                for (int p = 0; p < W; ++p) {
-                    const size_t i = (size_t)h * W + p;
-                    ua.peer[p] = xpeer(sl.xrecv, sl.xl.roff[i], sl.xl.cap_in[i]);
-                }
-                ua.overflow = sl.overflow;
-                ua.all_active = &sl.S.ctl->all_active;
-                HIP_TRY(launch_unpack(ua, rn, std::max(1, s->grid / 8), s->stream));
-            }
-        }
-    } else if (xs != s->stream) {
-        HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_xfer[NH - 1], 0));
+        break;
+    case XKind::Slots:
+        for (int h = 0; h < x.NH; ++h)
+            for (Slab& sl : s->slab)
+                if ((rc = unpack_slots(sl, x, h, rn, s->stream))) return rc;
+        break;
+    default:  // Lists: read in place by the round kernel; None: nothing travelled but the halo planes
+        break;
     }
-    if (push && x.HS && (rc = halo_pack_expand(s, b, false, s->stream))) return rc;
+    if (x.push && x.HS && (rc = halo_pack_expand(s, x.b, false, s->stream))) return rc;
     return GP_OK;
 }
 

@@ -90,16 +90,17 @@ struct Slab {
     DevState S{};
     int rank = 0;
     uint32_t hi = 0;  // one past the last owned id
-    // Imp3D random-edge exchange (W > 1)
+    // random-edge / full-topology exchange (W > 1; which form: gp_sim::kplan.xkind)
+    // Imp3D gossip on the tile kernel (XKind::Slots): per local sender, its in-edge slot at the
+    // owner of its random edge's target and that owner's rank (k_make_pos; k_pack)
     uint32_t* pos = nullptr;
-    uint8_t* xdst = nullptr;  // owner rank of each local sender's random-edge target (k_pack)
+    uint8_t* xdst = nullptr;
     uint8_t* xsend = nullptr;
     uint8_t* xrecv = nullptr;
     uint32_t nedges = 0;
     XLayout xl;                        // capacities and byte layout of xsend / xrecv / xown (setup_exchange)
     unsigned int* overflow = nullptr;  // device flag
     // Imp3D push-sum over several ranks: sender-ordered lists (gp_xchg.hpp)
-    bool lists = false;
     uint32_t nt = 0;                   // the slab's tiles
     uint32_t tb[XMAXH + 1] = {};       // region h: tiles [tb[h], tb[h + 1])
     uint32_t* gw = nullptr;            // [tile * W + d]: first header word of the tile's segment
@@ -112,7 +113,6 @@ struct Slab {
     // all cleared at its start (launch_round_full_multi)
     uint8_t* xown = nullptr;
     // Imp3D gossip (column kernel) over several ranks: random-edge sends as bitmaps (gp_xchg.hpp)
-    bool bits = false;
     uint32_t* rbits_in = nullptr;      // receive bitmap: source a's chunk at bit ro[a]
     uint32_t* tgt = nullptr;           // local target of every receive-bitmap bit
     BitsLayout bl;                     // the chunks of the send and receive bitmaps (build_bits)
@@ -210,8 +210,10 @@ struct Scratch {
     }
 };
 
-// Imp3D gossip on the column kernel: random-edge deliveries are counted by their
-// senders (rq) and cross ranks as counts; no bitmap, in-edge tags or slots.
+// Imp3D gossip on the column kernel: random-edge deliveries are counted at their targets a
+// round ahead (rq) -- by local senders' atomics, and for senders on other ranks from the received
+// bitmaps (XKind::Bits, k_apply_bits); no random-edge bits, in-edge tags or slots.  Selects kernel
+// behaviour (the rq arrays and their seeding); the exchange is selected by kplan.xkind.
 inline bool col_gossip_counts(const DevState& S) { return S.topo == IMP3D && S.alg == GOSSIP && S.kernel == KERNEL_COL; }
 
 // gp_setup.hip

@@ -189,8 +189,8 @@ struct DevState {
     int32_t* c;
     // gossip, Imp3D, column kernel: random-edge rumours each local node receives, by
     // round parity, indexed from lo -- counted a round ahead by the senders (atomics
-    // from local senders in k_gossip_col, the exchange's counts from remote ones in
-    // k_unpack) and read (then zeroed) by the receiver
+    // from local senders in k_gossip_col, one per received bit from remote ones in
+    // k_apply_bits) and read (then zeroed) by the receiver
     uint32_t* rq[2];
     uint32_t rq8;         // rq holds one byte per node (four per word) instead of one word
     // gossip column kernel across ranks (gp_xchg.hpp, bitmaps): per local sender its
@@ -226,10 +226,9 @@ struct DevState {
     // (= lo - halo); c, in_off and rbits are indexed from lo
     uint32_t lo, nloc, base;
     uint32_t ext_lo, ext_hi;  // ids the node arrays hold: [lo - halo, lo + nloc + halo) within [0, P)
-    // Imp3D random edges from senders on other ranks, per local in-edge:
-    // round tag (the round the message was delivered for) and the message
+    // Imp3D gossip on the tile kernel across ranks: per local in-edge, the round a remote
+    // sender's rumour was delivered for (k_unpack)
     uint32_t* rtag;
-    double2* rmsg;
     // Imp3D push-sum across ranks (sender-ordered lists, gp_xchg.hpp): per local in-edge
     // whose sender lives on another rank, its list key (64 * header word + bit) in this
     // rank's received header region; the received headers and messages of the round
@@ -287,7 +286,6 @@ struct RoundArgs {
     const uint32_t* in_srcd; // in_src with the sender's deg - 4 in bits 30-31, or null
     const uint8_t* ind4;     // nibble in-degrees (DevState::ind4), offset so that ind4 + j / 2 is node j's byte
     const uint32_t* rtag;    // per local in-edge: round of the delivered remote message (gossip)
-    const double2* rmsg;
     const uint32_t* rk;      // push-sum: per local in-edge, the remote sender's list key (DevState::rk)
     const XHdr* xhdr;        // push-sum: the received header words / messages of the round
     const double2* xvals;
@@ -331,7 +329,7 @@ struct WaveArgs {
     uint8_t* nbn;
     int32_t* c;
     uint32_t* rq_cur;        // Imp3D gossip: this round's random-edge deliveries per local node (read, then zeroed)
-    uint32_t* rq_next;       // next round's, counted by local senders with atomics (remote ones: k_unpack)
+    uint32_t* rq_next;       // next round's, counted by local senders with atomics (remote ones: k_apply_bits)
     uint32_t rq8;            // byte counters (DevState::rq8)
     const uint32_t* rnd;     // random edge of each local sender (id - lo)
     const uint32_t* rtg;     // several ranks: local target or send-bitmap bit of it (DevState::rtg)

@@ -1,5 +1,6 @@
-// gp_kernel_plan.hpp -- which round kernel a run gets: kernel variant, tile walk, grid, size class
-// and whether rounds run region by region (kernel_plan), decided from the run's shape, a handful of
+// gp_kernel_plan.hpp -- which round kernel a run gets: kernel variant, tile walk, grid, size class,
+// whether rounds run region by region, and with the kernel the form in which its messages cross
+// ranks (kernel_plan), decided from the run's shape, a handful of
 // integers the device and the compiled kernels report (KernelFacts, gathered by
 // gather_kernel_facts) and the experiments build's overrides (KernelOverrides, read once at create
 // by read_overrides, gp_setup.hip).  The rules are measured defaults; the position of each
@@ -70,6 +71,7 @@ struct KernelOverrides {
 
 struct KernelPlan {
     int kernel = KERNEL_TILE;
+    XKind xkind = XKind::None;   // the exchange across ranks (exchange_kind)
     uint32_t col_xsegs = 1;
     uint32_t walk = 0, wx = 8, wide = 0;
     int grid = 1;
@@ -135,6 +137,17 @@ inline int plan_variant(const RunShape& r, bool block_ok, const KernelOverrides&
         else if (*ov.kernel == KERNEL_BLOCK && block_ok) kernel = KERNEL_BLOCK;
     }
     return kernel;
+}
+
+// How this run's random-edge / full-topology messages cross ranks (XKind, gp_plan.hpp).  kernel:
+// plan_variant's answer, overrides applied -- the gossip column kernel sets bits itself, the tile
+// kernel reads in-edge tags.
+inline XKind exchange_kind(const RunShape& r, int kernel) {
+    if (r.world < 2) return XKind::None;
+    if (r.topology == RunShape::Imp3D)
+        return r.push() ? XKind::Lists : kernel == KERNEL_COL ? XKind::Bits : XKind::Slots;
+    if (r.topology == RunShape::Full) return r.push() ? XKind::FullBins : XKind::Slots;
+    return XKind::None;  // line / 3D: halo planes only
 }
 
 // The walk and its x-window, before walk 3 has been checked against the resident grid.
@@ -204,6 +217,7 @@ inline KernelPlan kernel_plan(const RunShape& r, const KernelFacts& f, const Ker
     int64_t cap = (int64_t)f.cus * 64;
     const bool block_ok = block_plan_wanted(r, f.cus, p.bplan) && f.block_resident;
     p.kernel = plan_variant(r, block_ok, ov);
+    p.xkind = exchange_kind(r, p.kernel);
     if (r.topology != RunShape::Full && p.kernel == KERNEL_COL) {
         // gossip: exactly the resident grid (a persistent sweep), a multiple of the 8 XCDs
         cap = (int64_t)f.cus * f.col_blocks_per_cu;

@@ -320,7 +320,8 @@ inline size_t halo_buf_slots(uint32_t n, uint32_t cap) { return (size_t)((n + HA
 
 // ---- buffer shapes
 // One rank pair's slot buffer (XPeer, gp_xchg.hpp): [count u32 | pad to 16 B][slots: cap u32 |
-// pad][vals: cap (s, w), push-sum only].
+// pad][vals: cap (s, w), with `push` only -- no run asks for it: the slot buffers carry gossip
+// alone since push-sum went to lists and bins, and setup_exchange passes push = false].
 constexpr size_t XBUF_SLOTS_OFF = 16;
 inline size_t xbuf_vals_off(uint32_t cap) { return XBUF_SLOTS_OFF + align16((size_t)cap * 4); }
 inline size_t xbuf_bytes(uint32_t cap, bool push) { return cap ? xbuf_vals_off(cap) + (push ? (size_t)cap * 16 : 0) : 0; }
@@ -441,11 +442,20 @@ struct XLayout {
     uint32_t xnv = 0;                // message slots in the vals region (at least 1)
 };
 
-enum class XKind { Lists, Slots, FullBins };  // Imp3D push-sum; gossip; full push-sum
+// The form in which a run's random-edge / full-topology messages cross ranks, decided once per run
+// (exchange_kind, gp_kernel_plan.hpp -> KernelPlan::xkind):
+//   None      one rank, and line / 3D at any world: halo planes only
+//   Lists     Imp3D push-sum: sender-ordered lists, read in place (k_list_pack)
+//   Bits      Imp3D gossip on the column kernel: one bit per remote edge (k_gossip_col, k_apply_bits)
+//   Slots     Imp3D gossip on the tile kernel (k_pack / k_unpack) and full gossip (gp_full.hip):
+//             in-edge slots / receiver ids in per-pair buffers with an in-band count
+//   FullBins  full push-sum: every destination's coarse bins (gp_fullbin.hip)
+enum class XKind { None, Lists, Bits, Slots, FullBins };
 
 // Rank a's layout from caps[(h * W + a) * W + b], the capacity of region h's buffer a -> b
-// (every rank's).  Lists: list_nw; rregions > 1: one receive buffer per round parity.  Slots:
-// push adds the vals part (XPeer).  FullBins: the coarse bins of every destination, 2^s1
+// (every rank's); kind: Lists, Slots or FullBins (None and Bits have no such buffers).  Lists:
+// list_nw; rregions > 1: one receive buffer per round parity.  Slots: push adds the vals part
+// (xbuf_bytes; unused by the runs).  FullBins: the coarse bins of every destination, 2^s1
 // receivers each (bounds, full_bin_multi_s1).  False (lists): a vals region beyond 2^32 slots.
 inline bool exchange_layout(XKind kind, const std::vector<uint32_t>& caps, const std::vector<uint32_t>& list_nw,
                             const std::vector<uint32_t>& bounds, int W, int NH, int a, uint32_t rregions, bool push,

@@ -116,7 +116,6 @@ int alloc_slab(gp_sim* s, Slab& sl, int r) {
     S.ext_hi = r < W - 1 ? hi + s->halo : hi;
     S.base = S.ext_lo & ~3u;  // 4-aligned: the tile kernels move node bytes as words
     S.rtag = nullptr;
-    S.rmsg = nullptr;
     S.rk = nullptr;
     S.rtg = nullptr;
     S.sbits = nullptr;

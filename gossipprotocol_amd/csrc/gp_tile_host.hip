@@ -43,7 +43,6 @@ RoundArgs make_round_args(const DevState& S, uint32_t round) {
     a.in_srcd = S.in_srcd;
     a.ind4 = S.ind4 ? S.ind4 - (S.lo / TILE) * (TILE / 2) : nullptr;
     a.rtag = S.rtag;
-    a.rmsg = S.rmsg;
     a.rk = S.rk;
     a.xhdr = S.xhdr[round & 1];
     a.xvals = S.xvals[round & 1];

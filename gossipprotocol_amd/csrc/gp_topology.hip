@@ -87,7 +87,6 @@ int build_lists(gp_sim* s, const uint32_t* rnd_all, uint32_t* kk, const uint32_t
     for (Slab& sl : s->slab) {
         DevState& S = sl.S;
         const int r = sl.rank;
-        sl.lists = true;
         sl.nt = tiles_for(S.lo, S.nloc);
         for (int h = 0; h <= XMAXH; ++h) sl.tb[h] = tb[r][h];
         if ((rc = dev_alloc_t(s, &sl.gw, gw_all[r].size() + 1)) || (rc = dev_alloc_t(s, &sl.lwt, lwt_all[r].size() + 16)))
@@ -144,7 +143,6 @@ int build_bits(gp_sim* s, const uint32_t* src, const uint32_t* recv, const uint3
     for (Slab& sl : s->slab) {
         DevState& S = sl.S;
         const int me = sl.rank;
-        sl.bits = true;
         if (!bits_layout(n, me, sl.bl)) {
             set_err("internal: random-edge bitmaps beyond 2^31 bits");
             return GP_EINVAL;
@@ -187,8 +185,9 @@ int build_bits(gp_sim* s, const uint32_t* src, const uint32_t* recv, const uint3
 // and the exclusive scan of the per-receiver in-degrees the CSR offsets (in_off,
 // in_src in id order).  Every rank builds the global order (it is
 // deterministic; ranks own consecutive id ranges) and keeps its
-// receivers' slice; with several ranks, each local sender also learns the
-// position of its message in the destination's in-edge array (pos).
+// receivers' slice; with several ranks, what the run's exchange kind needs (kplan.xkind):
+// Slots -- each local sender the position of its message in the destination's in-edge array
+// (pos) and the destination (xdst); Lists -- build_lists; Bits -- build_bits.
 
 int build_imp3d(gp_sim* s) {
     const uint32_t P = (uint32_t)s->P;
@@ -219,7 +218,8 @@ int build_imp3d(gp_sim* s) {
     uint8_t* scan_tmp = nullptr;
     HIP_TRY(tmp_mem.alloc(&scan_tmp, scan_bytes ? scan_bytes : 4));
     HIP_TRY(exclusive_scan_u32(scan_tmp, scan_bytes, counts, off_all, (uint32_t)nkeys + 1, s->stream));
-    if (W > 1) {
+    const XKind kind = s->kplan.xkind;
+    if (kind == XKind::Slots || kind == XKind::Bits) {  // (the lists are keyed from the senders' side)
         HIP_TRY(tmp_mem.alloc(&inv, P));
         HIP_TRY(launch_inverse(src_sorted, P, inv, s->grid, s->stream));
     }
@@ -259,18 +259,17 @@ int build_imp3d(gp_sim* s) {
             const uint32_t wide_at = s->exp.ind4_wide.value_or(15);  // in-degree >= 15: the tile reads in_off (gp_ps_tile.hip; GP_IND4_WIDE)
             HIP_TRY(launch_pack_ind4(S, wide_at, s->grid, s->stream));
         }
-        if (W > 1 && !col_gossip_counts(S)) {  // (the gossip column kernel's bitmaps: build_bits)
-            // push-sum: sender-ordered lists (build_lists), no slots or tags; gossip tile kernel:
-            // {slot} entries and round tags (k_pack / k_unpack)
-            const bool slots = S.alg != PUSHSUM;
-            if ((rc = dev_alloc_t(s, &sl.xdst, (size_t)S.nloc + 64))) return rc;
-            if (slots && ((rc = dev_alloc_t(s, &sl.pos, S.nloc)) || (rc = dev_alloc_t(s, &S.rtag, ne))))
+        if (kind == XKind::Slots) {
+            // gossip tile kernel across ranks: every sender's {slot} entry and its destination
+            // (k_pack), the in-edges' round tags (k_unpack)
+            if ((rc = dev_alloc_t(s, &sl.xdst, (size_t)S.nloc + 64)) || (rc = dev_alloc_t(s, &sl.pos, S.nloc)) ||
+                (rc = dev_alloc_t(s, &S.rtag, ne)))
                 return rc;
-            if (slots) HIP_TRY(hipMemsetAsync(S.rtag, 0xFF, sizeof(uint32_t) * (ne ? ne : 1), s->stream));
+            HIP_TRY(hipMemsetAsync(S.rtag, 0xFF, sizeof(uint32_t) * (ne ? ne : 1), s->stream));
             PosArgs pa{};
             pa.rnd = S.rnd;
             pa.inv = inv;
-            pa.pos = slots ? sl.pos : nullptr;
+            pa.pos = sl.pos;
             pa.xdst = sl.xdst;
             pa.lo = S.lo;
             pa.nloc = S.nloc;
@@ -282,10 +281,10 @@ int build_imp3d(gp_sim* s) {
         }
     }
     // (iota, the sort's value input, is free again: the lists' key scratch)
-    if (W > 1 && s->cfg.algorithm == GP_PUSHSUM && (rc = build_lists(s, rnd_all, iota, src_sorted, edge0))) return rc;
+    if (kind == XKind::Lists && (rc = build_lists(s, rnd_all, iota, src_sorted, edge0))) return rc;
     // (counts, off_all -- copied into the slabs' in_off -- and iota are free again: the bitmaps'
     // scratch, in stream order after those copies)
-    if (W > 1 && col_gossip_counts(S0) && (rc = build_bits(s, src_sorted, keys_sorted, inv, edge0, counts, off_all, iota)))
+    if (kind == XKind::Bits && (rc = build_bits(s, src_sorted, keys_sorted, inv, edge0, counts, off_all, iota)))
         return rc;
     HIP_TRY(hipStreamSynchronize(s->stream));
     return GP_OK;

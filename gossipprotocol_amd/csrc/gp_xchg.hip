@@ -2,22 +2,18 @@
 // exchange of Imp3D slabs, the rank-sum of the round bookkeeping for in-process
 // ranks, and the setup kernels that cut the global topology into slabs.
 //
-// Random edges cross slabs (7/8 of them at 8 ranks).  After round r every rank
-// packs, per destination rank, the messages of its senders that chose their
-// random edge for round r+1 (dir byte == DIR_RANDOM, written by the round
-// kernel): {slot, (s, w)} where `slot` is the message's in-edge position in the
-// destination's receiver-sorted CSR (static, precomputed) -- or, for gossip on the
-// column kernel, {target's local id}: a rumour count the receiver adds to its
-// next-round delivery counter (integer, so order-free).  Buffers have a
-// fixed capacity per rank pair (expected count + 12 sigma), so
-// RCCL moves fixed sizes on the stream with no host synchronisation; the
-// in-band count says how many entries are real, and an overflow is recorded
-// and fails the run loudly.  The receiver scatters each message to
-// rmsg[slot] and, for gossip and during push-sum activation, rtag[slot] = r+1;
-// its round kernel reads the tag instead of the sender's Philox draw (once every
-// node is active a push-sum sender's draw alone decides, remote or not).  Entry
-// order inside a buffer does not matter: every
-// message carries its slot, so results are independent of the atomics' order.
+// Random edges cross slabs (7/8 of them at 8 ranks), in the form the run's exchange kind
+// names (XKind, gp_plan.hpp): push-sum as sender-ordered lists (k_list_pack, below), gossip
+// on the column kernel as bitmaps (k_apply_bits, below), gossip on the tile kernel as slots:
+// after round r every rank packs, per destination rank, one entry for each of its senders that
+// chose its random edge for round r+1 (dir byte == DIR_RANDOM, written by the round kernel):
+// {slot}, the sender's in-edge position in the destination's receiver-sorted CSR (static,
+// precomputed: k_make_pos).  Buffers have a fixed capacity per rank pair (expected count +
+// 12 sigma), so RCCL moves fixed sizes on the stream with no host
+// synchronisation; the in-band count says how many entries are real, and an overflow is
+// recorded and fails the run loudly.  The receiver sets rtag[slot] = r+1 (k_unpack); its round
+// kernel reads the tag instead of the sender's Philox draw.  Entry order inside a buffer does
+// not matter: every entry names its slot, so results are independent of the atomics' order.
 #include <algorithm>
 
 #include "gp_xchg.hpp"
@@ -49,7 +45,7 @@ struct SlabTable {
 // and round at world 8, against 2.2 ms for the round kernel.)
 //
 // Sweep 2 takes 8 senders per thread at a time: their run slots (LDS atomics),
-// then every slot / payload load of the 8 at once, then the stores.  The loads
+// then the entry loads of the 8 at once, then the stores.  The loads
 // are buffer loads over the block's senders; a sender without a message loads
 // from past the end of the buffer, which returns 0 and touches no memory -- so
 // no load sits under a branch (the compiler would wait for each in turn) and
@@ -58,7 +54,8 @@ struct SlabTable {
 // load per message).
 // Wave priority raised (s_setprio 1) while k_pack / k_unpack issue their loads.  C5 at W = 8
 // virtual ranks, same box, alternated: pack 4.97-4.99 -> 4.83 ms and unpack 5.59-5.73 ->
-// 5.36-5.71 ms over the 8 slabs (profiles/r04/setprio_xchg.txt)
+// 5.36-5.71 ms over the 8 slabs (profiles/r04/setprio_xchg.txt; measured when these kernels also
+// carried push-sum's (s, w), as were the 15.4 / 2.2 ms above)
 template <int P>
 __device__ __forceinline__ void xchg_prio() {
     __builtin_amdgcn_s_setprio(P);
@@ -77,24 +74,20 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, uint32
 __global__ __launch_bounds__(256) void k_pack(PackArgs a) {
     __shared__ uint32_t cnt[XMAXW], off[XMAXW], cap[XMAXW];
     __shared__ uint32_t* oslots[XMAXW];
-    __shared__ double2* ovals[XMAXW];
-    __shared__ uint32_t bnd[XMAXW + 1];
     const uint32_t r0 = a.s_lo + blockIdx.x * PACK_RANGE;
     if (r0 >= a.s_hi) return;
     if (threadIdx.x < XMAXW) {
         cnt[threadIdx.x] = 0u;
         if (threadIdx.x < (uint32_t)a.W) {
             oslots[threadIdx.x] = a.peer[threadIdx.x].slots;
-            ovals[threadIdx.x] = a.peer[threadIdx.x].vals;
             cap[threadIdx.x] = a.peer[threadIdx.x].cap;
         }
     }
-    if (threadIdx.x <= (uint32_t)a.W) bnd[threadIdx.x] = a.bounds[threadIdx.x];
     __syncthreads();
-    const uint32_t me = (uint32_t)a.me;
     const uint32_t last = a.s_hi - 1;
-    // destination rank per sender, a nibble each; `me` means "no message" (a sender never
-    // packs for its own rank, so the value is free for every world size up to XMAXW = 16)
+    // destination rank per sender, a nibble each; this rank's own number means "no message" (a
+    // sender never packs for its own rank, so the value is free for every world size up to
+    // XMAXW = 16)
     const uint32_t none = (uint32_t)a.me;
     uint32_t dst[PACK_PER / 8];
 #pragma unroll
@@ -113,7 +106,7 @@ __global__ __launch_bounds__(256) void k_pack(PackArgs a) {
         for (int h = 0; h < 8; ++h) {
             const uint32_t li = r0 + (g * 8 + h) * 256u + threadIdx.x;
             uint32_t d = none;
-            if (li < a.s_hi && (b[h] & DIR_MASK) == DIR_RANDOM && t[h] != me) {
+            if (li < a.s_hi && (b[h] & DIR_MASK) == DIR_RANDOM && t[h] != none) {
                 d = t[h];
                 atomicAdd(&cnt[d], 1u);
             }
@@ -130,14 +123,11 @@ __global__ __launch_bounds__(256) void k_pack(PackArgs a) {
     // (uniform values kept in scalar registers: a resource in vector registers costs a
     // readfirstlane loop around every buffer load)
     const uint32_t nr = __builtin_amdgcn_readfirstlane(min(PACK_RANGE, a.s_hi - r0));
-    const uint32_t sw0 = __builtin_amdgcn_readfirstlane(a.lo + r0 - a.base);
-    // the entry: the in-edge slot at the destination, or (counts mode) the random edge's target
-    const __amdgpu_buffer_rsrc_t rs_ent = buf_rsrc((a.counts ? a.rnd : a.pos) + r0, nr * 4u);
-    const __amdgpu_buffer_rsrc_t rs_sw = buf_rsrc(a.swn + sw0, a.push ? nr * 16u : 0u);
+    // the entry: the sender's in-edge slot at the destination
+    const __amdgpu_buffer_rsrc_t rs_ent = buf_rsrc(a.pos + r0, nr * 4u);
 #pragma unroll
     for (int g = 0; g < PACK_PER / 8; ++g) {
         uint32_t d[8], idx[8], ent[8];
-        double2 v[8];
 #pragma unroll
         for (int h = 0; h < 8; ++h) {
             d[h] = (dst[g] >> (4 * h)) & 15u;
@@ -147,28 +137,21 @@ __global__ __launch_bounds__(256) void k_pack(PackArgs a) {
 #pragma unroll
         for (int h = 0; h < 8; ++h) {
             const uint32_t q = (g * 8 + h) * 256u + threadIdx.x;  // sender r0 + q
-            const bool m = d[h] != none;
-            ent[h] = __builtin_amdgcn_raw_buffer_load_b32(rs_ent, m ? q * 4u : BUF_NONE, 0, 0);
-            const auto x = __builtin_amdgcn_raw_buffer_load_b128(rs_sw, m ? q * 16u : BUF_NONE, 0, 0);
-            v[h] = __builtin_bit_cast(double2, x);
+            ent[h] = __builtin_amdgcn_raw_buffer_load_b32(rs_ent, d[h] != none ? q * 4u : BUF_NONE, 0, 0);
         }
         xchg_prio<0>();
 #pragma unroll
         for (int h = 0; h < 8; ++h) {
             if (d[h] == none) continue;
             const uint32_t k = d[h];
-            if (idx[h] < cap[k]) {
-                *gptr(oslots[k] + idx[h]) = a.counts ? ent[h] - bnd[k] : ent[h];
-                if (a.push) st_global(ovals[k] + idx[h], v[h]);
-            } else {
-                atomicOr(a.overflow, 1u);
-            }
+            if (idx[h] < cap[k]) *gptr(oslots[k] + idx[h]) = ent[h];
+            else atomicOr(a.overflow, 1u);
         }
     }
 }
 
-// blockIdx.y = source rank.  A thread owns UNP entries UNP_STRIDE apart: their
-// slots and payloads are loaded together (all in flight), then the scatters.  The
+// blockIdx.y = source rank.  A thread owns UNP entries 256 apart: their
+// slots are loaded together (all in flight), then the tags stored.  The
 // grid covers the largest buffer's capacity (launch_unpack), so no thread loops.
 constexpr int UNP = 4;
 constexpr uint32_t UNP_BLOCK = 256u * UNP;
@@ -180,31 +163,17 @@ __global__ __launch_bounds__(256) void k_unpack(UnpackArgs a, uint32_t round) {
     const uint32_t n = min(sent, a.peer[p].cap);
     const uint32_t k0 = blockIdx.x * UNP_BLOCK + threadIdx.x;
     if (k0 >= n) return;
-    // push-sum with every node active: the round kernels decide remote senders by their
-    // Philox draw and read no tag (all_active only ever goes 0 -> 1, and a round kernel
-    // reads it after this unpack); gossip and the activation phase need the tags
-    const bool tags = !a.push || __hip_atomic_load(a.all_active, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
     uint32_t slot[UNP];
-    double2 v[UNP];
     xchg_prio<1>();
 #pragma unroll
-    for (int u = 0; u < UNP; ++u) {  // clamped: every load unconditional
-        const uint32_t k = min(k0 + u * 256u, n - 1u);
-        slot[u] = a.peer[p].slots[k];
-        if (a.push) v[u] = a.peer[p].vals[k];
-    }
+    for (int u = 0; u < UNP; ++u)  // clamped: every load unconditional
+        slot[u] = a.peer[p].slots[min(k0 + u * 256u, n - 1u)];
     xchg_prio<0>();
 #pragma unroll
     for (int u = 0; u < UNP; ++u) {
         if (k0 + u * 256u >= n) break;
         const uint32_t e = slot[u];
-        if (e >= a.nedges) continue;  // never: slots are in-edge positions (or nodes) of this rank
-        if (a.rq) {  // gossip column kernel: a rumour for local node `e` next round (integer count)
-            rq_add(a.rq, a.rq8, e);
-            continue;
-        }
-        if (tags) a.rtag[e] = round;
-        if (a.push) a.rmsg[e] = v[u];
+        if (e < a.nedges) a.rtag[e] = round;  // (never beyond: slots are in-edge positions of this rank)
     }
 }
 
@@ -595,7 +564,7 @@ __global__ __launch_bounds__(256) void k_make_pos(PosArgs a) {
     for (uint32_t li = blockIdx.x * 256 + threadIdx.x; li < a.nloc; li += gridDim.x * 256) {
         const uint32_t own = owner_of(a.rnd[li], a.bounds, a.W);
         a.xdst[li] = (uint8_t)own;
-        if (a.pos) a.pos[li] = own == (uint32_t)a.me ? 0xFFFFFFFFu : a.inv[a.lo + li] - a.edge0[own];
+        a.pos[li] = own == (uint32_t)a.me ? 0xFFFFFFFFu : a.inv[a.lo + li] - a.edge0[own];
     }
 }
 
@@ -624,14 +593,12 @@ __global__ __launch_bounds__(256) void k_expect(ExpectArgs a) {
 }
 
 // ---------------------------------------------------------------- launchers
-hipError_t launch_pack(const PackArgs& a, int grid, hipStream_t st) {
-    (void)grid;
+hipError_t launch_pack(const PackArgs& a, hipStream_t st) {
     const uint32_t blocks = a.s_hi > a.s_lo ? (a.s_hi - a.s_lo + PACK_RANGE - 1) / PACK_RANGE : 0u;
     if (blocks) hipLaunchKernelGGL(k_pack, dim3(blocks), dim3(256), 0, st, a);
     return hipGetLastError();
 }
-hipError_t launch_unpack(const UnpackArgs& a, uint32_t round, int grid, hipStream_t st) {
-    (void)grid;
+hipError_t launch_unpack(const UnpackArgs& a, uint32_t round, hipStream_t st) {
     uint32_t cap = 0;
     for (int p = 0; p < a.W; ++p)
         if (p != a.me) cap = std::max(cap, a.peer[p].cap);

@@ -7,40 +7,32 @@
 
 namespace gp {
 
-// One rank pair's exchange buffer: [count u32 | pad][slots: cap u32][vals: cap (s, w)].
+// One rank pair's slot buffer (XKind::Slots: Imp3D gossip on the tile kernel, full gossip):
+// [count u32 | pad][slots: cap u32].
 struct XPeer {
     uint32_t* cnt;
     uint32_t* slots;
-    double2* vals;
     uint32_t cap;
 };
 
+// Imp3D gossip on the tile kernel across ranks (k_pack / k_unpack, gp_xchg.hip).
 struct PackArgs {
     const uint8_t* nbn;   // node bytes of the round being prepared (local array, id - base)
-    const double2* swn;   // (s, w) of that round (local array, id - base)
-    const uint32_t* rnd;  // random edge of each local sender (id - lo)
-    const uint8_t* xdst;  // owner rank of that edge's target (id - lo)
-    const uint32_t* pos;  // its slot in the destination's in-edge array (id - lo; null in counts mode)
+    const uint8_t* xdst;  // owner rank of each local sender's random-edge target (id - lo)
+    const uint32_t* pos;  // the entry: that sender's slot in the owner's in-edge array (id - lo)
     uint32_t lo, nloc, base;
     uint32_t s_lo, s_hi;  // the senders packed by this launch (local ids, one exchange region)
-    int W, me, push;
-    int counts;           // gossip column kernel: the entry is the target's local id at its owner
-                          // (a delivery count, k_unpack adds it to rq), not an in-edge slot
-    uint32_t bounds[XMAXW + 1];
+    int W, me;
     XPeer peer[XMAXW];    // send side
     unsigned int* overflow;
 };
 
 struct UnpackArgs {
-    uint32_t* rtag;
-    double2* rmsg;
-    uint32_t* rq;         // counts mode (gossip column kernel): next round's deliveries per local node
-    uint32_t rq8;         // (byte counters, DevState::rq8)
-    uint32_t nedges;      // entries must be below this bound (in-edges; counts mode: local nodes)
-    int W, me, push;
+    uint32_t* rtag;       // per local in-edge: the round a remote sender's rumour is delivered for
+    uint32_t nedges;      // entries must be below this bound (this rank's in-edges)
+    int W, me;
     XPeer peer[XMAXW];    // receive side
     unsigned int* overflow;  // set when a sender packed more messages than the buffer holds
-    const unsigned int* all_active;  // Ctl::all_active of this rank (push-sum: no tags once set)
 };
 
 struct ZeroArgs {
@@ -56,8 +48,8 @@ struct SumArgs {
 struct PosArgs {
     const uint32_t* rnd;  // local senders' random edges
     const uint32_t* inv;  // global sorted position of every sender
-    uint32_t* pos;        // may be null (counts mode)
-    uint8_t* xdst;
+    uint32_t* pos;        // out: the sender's slot in its target's owner's in-edge array (~0: local target)
+    uint8_t* xdst;        // out: that owner's rank
     uint32_t lo, nloc;
     int W, me;
     uint32_t bounds[XMAXW + 1];
@@ -196,8 +188,8 @@ hipError_t launch_list_pack(const ListPackArgs& a, hipStream_t st);
 hipError_t launch_gather_keys(const uint32_t* key, const uint32_t* src, uint32_t n, uint32_t* out, int grid,
                               hipStream_t st);
 
-hipError_t launch_pack(const PackArgs& a, int grid, hipStream_t st);
-hipError_t launch_unpack(const UnpackArgs& a, uint32_t round, int grid, hipStream_t st);
+hipError_t launch_pack(const PackArgs& a, hipStream_t st);
+hipError_t launch_unpack(const UnpackArgs& a, uint32_t round, hipStream_t st);
 hipError_t launch_zero_counts(const ZeroArgs& z, hipStream_t st);
 hipError_t launch_sum_xchg(const SumArgs& s, hipStream_t st);
 hipError_t launch_topo_rnd_range(uint32_t k0, uint32_t k1, uint32_t P, uint32_t first, uint32_t n, uint32_t* out,

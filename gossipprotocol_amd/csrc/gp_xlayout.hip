@@ -5,17 +5,19 @@
 
 // Fixed-capacity exchange buffers per rank pair: capacity = expected messages
 // per round + 12 sigma + 64 (never more than the pair's random edges).  Push-sum
-// exchanges have two regions per pair, one per half of the sender's senders
-// (s->xhalves), moved separately on the exchange stream so that one half's
-// transfer overlaps the other half's packing / unpacking (full topology:
-// launch_round_full_multi; Imp3D: exchange).
+// exchanges cut each slab's senders into regions (kplan.xregions -> s->xhalves: the lists'
+// tiles in XREGIONS or eight regions, the full topology's fine tiles in two), one buffer per
+// pair and region, moved separately on the exchange stream so that one region's transfer
+// overlaps the others' packing (full topology: launch_round_full_multi; Imp3D: exchange,
+// launch_round_regions).  Gossip has one region.
 int setup_exchange(gp_sim* s) {
     const int W = s->world;
+    const XKind kind = s->kplan.xkind;
     const bool push = s->cfg.algorithm == GP_PUSHSUM;
     const bool full = s->cfg.topology == GP_FULL;
-    if (!s->slab.empty() && s->slab[0].bits) {  // gossip column kernel: fixed-size bitmaps (build_bits)
+    for (Slab& sl : s->slab) sl.overflow = &sl.S.ctl->overflow;
+    if (kind == XKind::Bits) {  // gossip column kernel: fixed-size bitmaps (build_bits)
         s->xhalves = 1;
-        for (Slab& sl : s->slab) sl.overflow = &sl.S.ctl->overflow;
         return GP_OK;
     }
     const int NH = s->kplan.xregions;
@@ -62,7 +64,7 @@ int setup_exchange(gp_sim* s) {
             ea.rnd = S.rnd;
             ea.lo = S.lo;
             ea.nloc = S.nloc;
-            xregion(S.lo, S.nloc, sl.lists, sl.tb, NH, h, ea.s_lo, ea.s_hi);
+            xregion(S.lo, S.nloc, kind == XKind::Lists, sl.tb, NH, h, ea.s_lo, ea.s_hi);
             ea.W = W;
             ea.me = sl.rank;
             for (int w = 0; w <= W; ++w) ea.bounds[w] = s->bounds[w];
@@ -97,21 +99,21 @@ int setup_exchange(gp_sim* s) {
         }
     }
     // the layout of every rank's buffers from the capacities (exchange_layout, gp_plan.hpp):
-    // Imp3D push-sum sender-ordered lists (gp_xchg.hpp), gossip slot buffers, or full push-sum's
-    // coarse bins (own messages: straight to xrecv; the own share's second parity: Slab::xown)
+    // Imp3D push-sum sender-ordered lists (gp_xchg.hpp), gossip slot buffers (entries only: no
+    // vals part), or full push-sum's coarse bins (own messages: straight to xrecv; the own
+    // share's second parity: Slab::xown)
     int rc;
     for (Slab& sl : s->slab) {
-        const XKind kind = sl.lists ? XKind::Lists : full && push ? XKind::FullBins : XKind::Slots;
         XLayout& L = sl.xl;
-        if (!exchange_layout(kind, caps, s->list_nw, s->bounds, W, NH, sl.rank, sl.S.rregions, push, L)) {
+        if (!exchange_layout(kind, caps, s->list_nw, s->bounds, W, NH, sl.rank, sl.S.rregions, /* slot buffers' vals part */ false, L)) {
             set_err("internal: exchange vals region beyond 2^32 slots");
             return GP_EINVAL;
         }
         if ((rc = dev_alloc_t(s, &sl.xsend, L.send_bytes)) || (rc = dev_alloc_t(s, &sl.xrecv, L.recv_bytes))) return rc;
-        if (sl.lists && (rc = dev_alloc_t(s, &sl.xcnt, (size_t)NH * W))) return rc;
+        if (kind == XKind::Lists && (rc = dev_alloc_t(s, &sl.xcnt, (size_t)NH * W))) return rc;
         HIP_TRY(hipMemsetAsync(sl.xsend, 0, L.send_bytes ? L.send_bytes : 16, s->stream));
         HIP_TRY(hipMemsetAsync(sl.xrecv, 0, L.recv_bytes ? L.recv_bytes : 16, s->stream));
-        if (sl.lists) {
+        if (kind == XKind::Lists) {
             for (int k = 0; k < 2; ++k) {
                 sl.S.xhdr[k] = reinterpret_cast<const XHdr*>(sl.xrecv + k * L.xr_stride);
                 sl.S.xvals[k] = reinterpret_cast<const double2*>(sl.xrecv + k * L.xr_stride + L.hdr_in);
@@ -122,7 +124,6 @@ int setup_exchange(gp_sim* s) {
             if ((rc = dev_alloc_t(s, &sl.xown, L.own_bytes))) return rc;
             HIP_TRY(hipMemsetAsync(sl.xown, 0, L.own_bytes ? L.own_bytes : 16, s->stream));
         }
-        sl.overflow = &sl.S.ctl->overflow;
     }
     if (NH > 1) {  // the second stream and the events that order it with the compute stream
         HIP_TRY(hipStreamCreateWithFlags(&s->xstream, hipStreamNonBlocking));

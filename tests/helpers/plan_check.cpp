@@ -24,6 +24,7 @@
 //   layout kind(0 lists, 1 slots, 2 bins) W NH a rregions push bounds... caps... list_nw...
 //       -> ok send recv own hdr_in xr_stride xnv ; cap_out ; cap_in ; soff ; sbytes ; roff ;
 //          rbytes ; ooff ; lhdr ; lval ; rhdr ; rval ; vbase
+//   xkind topology algorithm world kernel  -> XKind (0 none, 1 lists, 2 bits, 3 slots, 4 bins)
 //   walk lo nloc g2 wx NR                  -> ok ; woff[h][0..8]... ; list
 //   kernel_plan topo alg P g W mode  cus col_blocks_per_cu res4 res_wide block_resident
 //               kernel xsegs walk wx wide rregions xregions fuse stage_cap no_full grid
@@ -213,6 +214,11 @@ int main() {
             put(L.rhdr);
             put(L.rval);
             put(L.vbase);
+        } else if (q == "xkind") {
+            RunShape r;
+            int kernel;
+            in >> r.topology >> r.algorithm >> r.world >> kernel;
+            std::printf(" %d", (int)exchange_kind(r, kernel));
         } else if (q == "walk") {
             uint32_t lo, nloc, wx;
             uint64_t g2;

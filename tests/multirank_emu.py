@@ -15,9 +15,10 @@ ranks only through the library's exchange plan:
     word {bitmap, base} per 64 entries of the static list and the used entries'
     (s, w) compacted in list order; the receiver finds a remote in-edge's message
     from its list key (64 * header word + bit, build_lists) as base + the used
-    entries below it.  Gossip (the column kernel's counts mode) {target's local
-    id}, a rumour the receiver counts for the next round -- local senders count
-    theirs at the target directly (k_gossip_col);
+    entries below it.  Gossip: {target's local id}, a rumour the receiver counts
+    for the next round -- local senders count theirs at the target directly
+    (k_gossip_col); the library moves the same deliveries as one bit per remote
+    edge (column kernel) or as in-edge slots (tile kernel), gp_plan.hpp XKind;
   * bookkeeping: {alerts, newly active, injector pick converged} summed over
     ranks (k_finalize_pre / all-reduce / k_finalize_post); the gossip
     injector's live list is replicated on every rank;
@@ -406,18 +407,12 @@ class RankSim:
         off_all = np.zeros(P + 1, dtype=np.int64)
         np.add.at(off_all, rnd_all + 1, 1)
         off_all = np.cumsum(off_all)
-        inv = np.empty(P, dtype=np.int64)
-        inv[order] = np.arange(P)
         edge0 = off_all[self.bounds]
         self.in_off = off_all[self.lo:self.hi + 1] - edge0[self.rank]
         self.in_src = order[edge0[self.rank]:edge0[self.rank + 1]]
         self.rnd = rnd_all[self.lo:self.hi]
         self.owner = np.searchsorted(np.array(self.bounds[1:-1]), self.rnd, side="right")
-        # slot of each local sender's message in its target owner's in-edge array (k_make_pos)
-        self.pos = inv[self.lo:self.hi] - edge0[self.owner]
         ne = len(self.in_src)
-        self.rtag = np.full(ne, -1, dtype=np.int64)
-        self.rmsg = np.zeros((ne, 2))
         self.plan = None
         if self.alg == "push-sum" and self.W > 1:  # sender-ordered lists (build_lists)
             self.plan = ListPlan(P, self.g, self.W, self.bounds, rnd_all, self.G)
@@ -466,29 +461,16 @@ class RankSim:
             np.add.at(self.rq, self.rnd[mine] - self.lo, 1)
         if self.topo == "Imp3D" and self.W > 1 and self.plan is not None:
             self._exchange_lists()
-        elif self.topo == "Imp3D" and self.W > 1:
+        elif self.topo == "Imp3D" and self.W > 1:  # gossip: the remote senders' counts
             mydir = self.dir[self._local(self.ids)]
             send = (mydir == DIR_RANDOM) & (self.owner != self.rank)
-            packets = {}
-            for p in range(self.W):
-                sel = send & (self.owner == p)
-                if self.alg == "push-sum":
-                    li = self._local(self.ids[sel])
-                    packets[p] = (self.pos[sel], self.s[li], self.w[li])
-                else:  # counts: the target's id local to its owner
-                    packets[p] = (self.rnd[sel] - self.bounds[p],)
+            # per destination, the targets' ids local to their owner
+            packets = {p: self.rnd[send & (self.owner == p)] - self.bounds[p] for p in range(self.W)}
             got = [None] * self.W
             d.all_gather_object(got, packets)
             for src, pk in enumerate(got):
-                if src == self.rank:
-                    continue
-                msg = pk[self.rank]
-                if self.alg == "push-sum":
-                    self.rtag[msg[0]] = rn
-                    self.rmsg[msg[0], 0] = msg[1]
-                    self.rmsg[msg[0], 1] = msg[2]
-                else:
-                    np.add.at(self.rq, msg[0], 1)
+                if src != self.rank:
+                    np.add.at(self.rq, pk[self.rank], 1)
         _ = torch  # gloo transport via torch.distributed
 
     def _exchange_lists(self):
@@ -558,12 +540,10 @@ class RankSim:
         local = (src >= self.lo) & (src < self.hi)
         sent = np.zeros(len(src), dtype=bool)
         sent[local] = self.dir[self._local(src[local])] == DIR_RANDOM
-        if self.plan is not None:  # push-sum: the received lists
+        if self.plan is not None:  # several ranks: the received lists (one rank: every sender is local)
             self.rslot = np.zeros(len(src), dtype=np.int64)
             if (~local).any():
                 sent[~local], self.rslot[~local] = self._list_lookup(self.rk[~local])
-        else:
-            sent[~local] = self.rtag[~local] == r
         return sent, local
 
     def _pushsum_round(self):
@@ -593,8 +573,6 @@ class RankSim:
             if self.plan is not None:
                 rs = np.where(sent & ~local, self.rslot, 0)
                 val_s[~local], val_w[~local] = self.xvals[rs[~local], 0], self.xvals[rs[~local], 1]
-            else:
-                val_s[~local], val_w[~local] = self.rmsg[~local, 0], self.rmsg[~local, 1]
             indeg = np.diff(self.in_off)
             for k in range(int(indeg.max()) if len(indeg) else 0):
                 has = indeg > k

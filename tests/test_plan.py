@@ -438,3 +438,32 @@ def test_kernel_plan_golden_holds_the_cases_where_a_rule_flips(kernel_plan_golde
                 else None) == {(False, 1)}
     errors = {ov["GP_GRID"] for _, _, ov, w in kernel_plan_golden if isinstance(w, str)}
     assert {"abc", "0", "-8", "8x", "99999999999999999999", "41"} <= errors
+
+
+# ---- the exchange kind (exchange_kind, gp_kernel_plan.hpp): XKind's integers
+X_NONE, X_LISTS, X_BITS, X_SLOTS, X_BINS = range(5)
+# (topology, algorithm): the kind for world > 1 by kernel variant (tile, col, block); world 1: none
+EXCHANGE_KINDS = {
+    ("line", "gossip"): (X_NONE, X_NONE, X_NONE),
+    ("line", "push-sum"): (X_NONE, X_NONE, X_NONE),
+    ("full", "gossip"): (X_SLOTS, X_SLOTS, X_SLOTS),
+    ("full", "push-sum"): (X_BINS, X_BINS, X_BINS),
+    ("3D", "gossip"): (X_NONE, X_NONE, X_NONE),
+    ("3D", "push-sum"): (X_NONE, X_NONE, X_NONE),
+    ("Imp3D", "gossip"): (X_SLOTS, X_BITS, X_SLOTS),
+    ("Imp3D", "push-sum"): (X_LISTS, X_LISTS, X_LISTS),
+}
+
+
+def test_exchange_kind_table(plan):
+    """One exchange kind per run: every topology x algorithm x world in {1, 2, 16} x kernel variant.
+    Halo-only runs and single ranks exchange nothing; only Imp3D gossip depends on the kernel (the
+    column kernel sets bits, the tile kernel reads in-edge tags)."""
+    topos = {"line": 0, "full": 1, "3D": 2, "Imp3D": 3}
+    algs = {"gossip": 0, "push-sum": 1}
+    cases = [(t, a, W, k) for t in topos for a in algs for W in (1, 2, 16) for k in ("tile", "col", "block")]
+    assert len(cases) == 4 * 2 * 3 * 3
+    got = plan([("xkind", topos[t], algs[a], W, KERNELS[k]) for t, a, W, k in cases])
+    for (t, a, W, k), (kind,) in zip(cases, got):
+        want = X_NONE if W == 1 else EXCHANGE_KINDS[t, a][("tile", "col", "block").index(k)]
+        assert kind == want, (t, a, W, k, kind, want)
