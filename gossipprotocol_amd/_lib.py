@@ -17,6 +17,7 @@ EXP_LIB_PATH = os.path.join(PKG_DIR, "libgossip_hip_exp.so")
 EXP_LIB_PATH = os.environ.get("GOSSIP_HIP_LIB_EXPERIMENT", EXP_LIB_PATH)
 
 GP_LINE, GP_FULL, GP_3D, GP_IMP3D = 0, 1, 2, 3
+GP_GRAPH = 4  # a caller-supplied graph: gp_ensemble_create_graph only, and it has no string
 GP_GOSSIP, GP_PUSHSUM = 0, 1
 GP_STATUS_CONVERGED, GP_STATUS_MAX_ROUNDS, GP_STATUS_RUNNING = 0, 1, 2
 GP_FLAG_KERNEL_TIMING = 1
@@ -78,6 +79,12 @@ class GpValues(C.Structure):
     """Values and weights every member of an ensemble starts from (gp_values)."""
     _fields_ = [("x", C.POINTER(C.c_double)), ("w", C.POINTER(C.c_double)), ("count", C.c_int64),
                 ("mean", C.c_double), ("reserved", C.c_int64)]
+
+
+class GpGraph(C.Structure):
+    """A directed graph in CSR form (gp_graph)."""
+    _fields_ = [("indptr", C.POINTER(C.c_int64)), ("indices", C.POINTER(C.c_uint32)), ("num_nodes", C.c_int64),
+                ("num_edges", C.c_int64), ("reserved", C.c_int64)]
 
 
 class GpSummary(C.Structure):
@@ -157,6 +164,9 @@ SIGNATURES = [
     ("gp_set_mean", _i32, [_vp, C.c_double]),
     ("gp_ensemble_create_values", _i32, [C.POINTER(GpConfig), C.POINTER(GpValues), C.POINTER(GpFaults),
                                          C.POINTER(GpTraceCfg), C.POINTER(C.c_uint64), _i64, C.POINTER(_vp)]),
+    ("gp_ensemble_graph_lds_bytes", _i64, [C.POINTER(GpGraph), _i32, _i32, _i32]),
+    ("gp_ensemble_create_graph", _i32, [C.POINTER(GpConfig), C.POINTER(GpGraph), C.POINTER(GpValues), C.POINTER(GpFaults),
+                                        C.POINTER(GpTraceCfg), C.POINTER(C.c_uint64), _i64, C.POINTER(_vp)]),
 ]
 
 _libs = {}

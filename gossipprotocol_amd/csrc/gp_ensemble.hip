@@ -6,7 +6,7 @@
 
 namespace gp {
 
-template hipError_t ens_setup_t<false, false>(int, int, uint32_t);
+template hipError_t ens_setup_t<false, false>(int, int, uint32_t, uint32_t);
 template hipError_t ens_launch_t<false, false>(int, int, const EnsArgs&, uint32_t, hipStream_t);
 
 }  // namespace gp

@@ -17,6 +17,9 @@ namespace gp {
 // and lives in gp_ensemble_shape.hpp, written over the public enums:
 static_assert(LINE == GP_LINE && FULL == GP_FULL && GRID3D == GP_3D && IMP3D == GP_IMP3D, "topology enums");
 static_assert(GOSSIP == GP_GOSSIP && PUSHSUM == GP_PUSHSUM, "algorithm enums");
+// A caller-supplied graph (SRS v1-G): a topology of the ensemble kernels alone.
+constexpr int GRAPH = ENS_GRAPH;
+static_assert(GRAPH == IMP3D + 1, "the graph follows the reference's four topologies");
 
 // Failure model (SRS v1-F): Philox streams and the per-member record
 // that persists between launches beside gp_member (whose `converged` carries the
@@ -86,6 +89,14 @@ struct EnsArgs {
     const double* x0;
     const double* w0;
     double mu;  // TRACE: what err_max is measured against; (P - 1) / 2 unless values were given
+    // GRAPH, SRS v1-G (gp_ensemble_create_graph): the out-CSR in the caller's order and, for push-sum, the
+    // transposed, deduplicated in-CSR (gp_graph.hpp), on the device; every array padded to a multiple of
+    // 8 bytes, which is how a launch stages them into LDS.  Null / 0 for the built-in topologies.
+    const uint32_t* g_out_off;  // P + 1
+    const uint16_t* g_out_nbr;  // g_eout
+    const uint32_t* g_in_off;   // P + 1
+    const uint16_t* g_in_nbr;   // g_ein
+    uint32_t g_eout, g_ein;
 };
 
 // The launch interface of one variant, defined in gp_ensemble_kernels.hpp and instantiated by
@@ -93,22 +104,24 @@ struct EnsArgs {
 // Setup raises the kernel's dynamic-LDS limit for population P, once per handle; launch runs
 // one workgroup per listed member.
 template <bool FAULTS, bool TRACE>
-hipError_t ens_setup_t(int topo, int alg, uint32_t P);
+hipError_t ens_setup_t(int topo, int alg, uint32_t P, uint32_t graph_lds);
 template <bool FAULTS, bool TRACE>
 hipError_t ens_launch_t(int topo, int alg, const EnsArgs& a, uint32_t nblocks, hipStream_t st);
 // (extern: the dispatchers below must not instantiate every variant in every unit)
-extern template hipError_t ens_setup_t<false, false>(int, int, uint32_t);
-extern template hipError_t ens_setup_t<true, false>(int, int, uint32_t);
-extern template hipError_t ens_setup_t<false, true>(int, int, uint32_t);
-extern template hipError_t ens_setup_t<true, true>(int, int, uint32_t);
+extern template hipError_t ens_setup_t<false, false>(int, int, uint32_t, uint32_t);
+extern template hipError_t ens_setup_t<true, false>(int, int, uint32_t, uint32_t);
+extern template hipError_t ens_setup_t<false, true>(int, int, uint32_t, uint32_t);
+extern template hipError_t ens_setup_t<true, true>(int, int, uint32_t, uint32_t);
 extern template hipError_t ens_launch_t<false, false>(int, int, const EnsArgs&, uint32_t, hipStream_t);
 extern template hipError_t ens_launch_t<true, false>(int, int, const EnsArgs&, uint32_t, hipStream_t);
 extern template hipError_t ens_launch_t<false, true>(int, int, const EnsArgs&, uint32_t, hipStream_t);
 extern template hipError_t ens_launch_t<true, true>(int, int, const EnsArgs&, uint32_t, hipStream_t);
 
-inline hipError_t ens_setup(EnsVariant v, int topo, int alg, uint32_t P) {
-    if (v.trace) return v.faults ? ens_setup_t<true, true>(topo, alg, P) : ens_setup_t<false, true>(topo, alg, P);
-    return v.faults ? ens_setup_t<true, false>(topo, alg, P) : ens_setup_t<false, false>(topo, alg, P);
+// graph_lds: GRAPH only, the image of the handle's graph (ens_graph_lds_bytes); else 0.
+inline hipError_t ens_setup(EnsVariant v, int topo, int alg, uint32_t P, uint32_t graph_lds) {
+    if (v.trace)
+        return v.faults ? ens_setup_t<true, true>(topo, alg, P, graph_lds) : ens_setup_t<false, true>(topo, alg, P, graph_lds);
+    return v.faults ? ens_setup_t<true, false>(topo, alg, P, graph_lds) : ens_setup_t<false, false>(topo, alg, P, graph_lds);
 }
 inline hipError_t ens_launch(EnsVariant v, int topo, int alg, const EnsArgs& a, uint32_t nblocks, hipStream_t st) {
     if (v.trace)

@@ -5,6 +5,7 @@
 
 #include "gp_host.hpp"
 #include "gp_ensemble.hpp"
+#include "gp_graph.hpp"
 #pragma GCC visibility push(hidden)
 #include "gp_summary_dev.hpp"
 #pragma GCC visibility pop
@@ -45,6 +46,27 @@ bool pair_ok(int32_t topology, int32_t algorithm) {
     return true;
 }
 
+// SRS v1-G: the LDS image of a member on `graph` (gp_ensemble_shape.hpp), or -1 with the message set when
+// the graph is inadmissible (gp_graph.hpp) or its image does not fit.  Host only.
+int64_t graph_image(const gp_graph* graph, int32_t algorithm, EnsVariant v) {
+    std::string why;
+    if (graph_validate(graph, (int64_t)ENS_GRAPH_POP_MAX, &why) != GRAPH_OK) {
+        set_err("%s", why.c_str());
+        return -1;
+    }
+    const int64_t e_in = graph_in_entries(graph);
+    const uint64_t bytes =
+        ens_graph_lds_bytes(algorithm, (uint64_t)graph->num_nodes, (uint64_t)graph->num_edges, (uint64_t)e_in, v);
+    if (bytes > ENS_LDS_MAX) {
+        set_err("graph: the LDS image of %lld nodes, %lld out-entries and %lld in-entries takes %llu bytes%s%s, more than "
+                "the %u a member may take (the adjacency must fit in one workgroup's LDS)",
+                (long long)graph->num_nodes, (long long)graph->num_edges, (long long)e_in, (unsigned long long)bytes,
+                v.faults ? ", failure layout" : "", v.trace ? ", trace layout" : "", ENS_LDS_MAX);
+        return -1;
+    }
+    return (int64_t)bytes;
+}
+
 // A trace buffer may take this much HBM (nseeds x capacity rows of 32 bytes).
 constexpr int64_t ENS_TRACE_BYTES_MAX = 1ll << 30;
 
@@ -71,6 +93,8 @@ struct gp_ensemble {
     SumAcc* d_sum = nullptr;       // gp_ensemble_summary: one record per member, allocated at the first call
     std::vector<EnsFaultRec> frec; // v.faults: host copy of args.f.frec, refreshed after every launch
     double mean = 0.0;             // mu of the summaries and the trace: (P - 1) / 2 unless values were given (SRS v1-V)
+    GraphCsr csr;                  // GP_GRAPH: the two CSRs until they are uploaded (SRS v1-G)
+    uint32_t graph_lds = 0;        // GP_GRAPH: the member's LDS image, adjacency included
 };
 
 namespace {
@@ -110,14 +134,44 @@ int launch(gp_ensemble* e, int64_t nrounds, bool init) {
     return GP_OK;
 }
 
+// One array of a CSR onto the device, padded with zeros to the multiple of 8 bytes the kernels stage.
+template <typename T>
+int upload_padded(gp_ensemble* e, const T** dev, std::vector<T>& host) {
+    host.resize((ens_up8((uint32_t)(host.size() * sizeof(T)))) / sizeof(T), T(0));
+    T* d = nullptr;
+    const int rc = ens_alloc(e, &d, host.size());
+    if (rc) return rc;
+    if (!host.empty())
+        HIP_TRY(hipMemcpyAsync(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, e->stream));
+    *dev = d;
+    return GP_OK;
+}
+
+// GP_GRAPH: both CSRs go up once; every launch stages them from there into LDS.
+int upload_graph(gp_ensemble* e) {
+    EnsArgs& a = e->args;
+    GraphCsr& c = e->csr;
+    a.g_eout = (uint32_t)c.out_nbr.size();
+    a.g_ein = (uint32_t)c.in_nbr.size();
+    int rc = upload_padded(e, &a.g_out_off, c.out_off);
+    if (!rc) rc = upload_padded(e, &a.g_out_nbr, c.out_nbr);
+    if (!rc) rc = upload_padded(e, &a.g_in_off, c.in_off);
+    if (!rc) rc = upload_padded(e, &a.g_in_nbr, c.in_nbr);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));  // (the host copies go away)
+    c = GraphCsr{};
+    return GP_OK;
+}
+
 int create(gp_ensemble* e, const uint64_t* seeds, const gp_values* values) {
     const int topo = e->cfg.topology, alg = e->cfg.algorithm;
     const size_t n = (size_t)e->nseeds, P = (size_t)e->P;
     HIP_TRY(hipSetDevice(e->cfg.device));
     HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    HIP_TRY(ens_setup(e->v, topo, alg, (uint32_t)P));
+    HIP_TRY(ens_setup(e->v, topo, alg, (uint32_t)P, e->graph_lds));
     EnsArgs& a = e->args;
     int rc = ens_alloc(e, &a.rec, n);
+    if (!rc && topo == GP_GRAPH) rc = upload_graph(e);
     if (!rc && e->v.trace) {
         // (the kernels write a row before anybody may read it, and the set-up launch every record)
         rc = ens_alloc(e, &a.t.rows, n * (size_t)a.t.capacity);
@@ -232,8 +286,10 @@ static int trace_ok(const char* who, const gp_trace_cfg* trace) {
 // gp_ensemble_create, gp_ensemble_create_faults (faults != null) and gp_ensemble_create_traced
 // (trace != null), their own arguments already checked.
 // values != null: gp_ensemble_create_values, its own fields but count already checked.
+// graph != null: gp_ensemble_create_graph, cfg->topology == GP_GRAPH already checked; the graph is checked here.
 static int ensemble_create(const gp_config* cfg, const gp_values* values, const gp_faults* faults,
-                           const gp_trace_cfg* trace, const uint64_t* seeds, int64_t nseeds, gp_ensemble** out) {
+                           const gp_trace_cfg* trace, const uint64_t* seeds, int64_t nseeds, gp_ensemble** out,
+                           const gp_graph* graph = nullptr) {
     if (!seeds) {
         set_err("gp_ensemble_create: seeds is null");
         return GP_EINVAL;
@@ -250,9 +306,22 @@ static int ensemble_create(const gp_config* cfg, const gp_values* values, const 
         set_err("gp_ensemble_create: max_rounds must be > 0 (an ensemble needs an explicit cap)");
         return GP_EINVAL;
     }
-    if (!pair_ok(cfg->topology, cfg->algorithm)) return GP_EINVAL;
+    if (!pair_ok(graph ? GP_LINE : cfg->topology, cfg->algorithm)) return GP_EINVAL;
+    const EnsVariant v{faults != nullptr, trace != nullptr};
     int64_t P = 0, T = 0, g = 0;
-    if (gp_resolve(cfg->num_nodes, cfg->topology, &P, &T, &g)) return GP_EINVAL;
+    int64_t graph_lds = 0;
+    if (graph) {  // SRS v1-G: P = T = the graph's nodes, no extra actor
+        graph_lds = graph_image(graph, cfg->algorithm, v);
+        if (graph_lds < 0) return GP_EINVAL;
+        if (cfg->num_nodes != graph->num_nodes) {
+            set_err("gp_ensemble_create_graph: cfg.num_nodes %lld is not the graph's num_nodes %lld",
+                    (long long)cfg->num_nodes, (long long)graph->num_nodes);
+            return GP_EINVAL;
+        }
+        P = T = graph->num_nodes;
+    } else if (gp_resolve(cfg->num_nodes, cfg->topology, &P, &T, &g)) {
+        return GP_EINVAL;
+    }
     if (P < 2) {
         set_err("gp_ensemble_create: a population of %lld has no edge", (long long)P);
         return GP_EINVAL;
@@ -261,8 +330,7 @@ static int ensemble_create(const gp_config* cfg, const gp_values* values, const 
         set_err("gp_ensemble_create_values: count %lld is not the population %lld", (long long)values->count, (long long)P);
         return GP_EINVAL;
     }
-    const EnsVariant v{faults != nullptr, trace != nullptr};
-    const int64_t cap = ens_max_nodes(cfg->topology, cfg->algorithm, v);
+    const int64_t cap = graph ? (int64_t)ENS_GRAPH_POP_MAX : ens_max_nodes(cfg->topology, cfg->algorithm, v);
     if (cfg->num_nodes > cap) {
         set_err("gp_ensemble_create: num_nodes %lld exceeds the ensemble cap %lld of this pair (one workgroup's LDS%s%s); "
                 "use gp_create", (long long)cfg->num_nodes, (long long)cap, faults ? ", failure layout" : "",
@@ -298,6 +366,10 @@ static int ensemble_create(const gp_config* cfg, const gp_values* values, const 
     e->nwords = (uint32_t)((T + 31) / 32);
     e->v = v;
     e->mean = values ? values->mean : (double)(P - 1) * 0.5;
+    if (graph) {
+        graph_build(graph, &e->csr);
+        e->graph_lds = (uint32_t)graph_lds;
+    }
     if (faults) {
         e->args.f.q_node = fault_threshold(faults->node_fail);
         e->args.f.q_drop = fault_threshold(faults->msg_drop);
@@ -364,18 +436,8 @@ int gp_ensemble_create_traced(const gp_config* cfg, const gp_faults* faults, con
     return ensemble_create(cfg, nullptr, faults, trace, seeds, nseeds, out);
 }
 
-int gp_ensemble_create_values(const gp_config* cfg, const gp_values* values, const gp_faults* faults,
-                              const gp_trace_cfg* trace, const uint64_t* seeds, int64_t nseeds, gp_ensemble** out) {
-    const char* who = "gp_ensemble_create_values";
-    if (!cfg || !out) {
-        set_err("%s: null argument", who);
-        return GP_EINVAL;
-    }
-    *out = nullptr;
-    if (!values) {
-        set_err("%s: values is null", who);
-        return GP_EINVAL;
-    }
+// gp_ensemble_create_values' checks of the values' own fields (count and entries are checked later).
+static int values_ok(const char* who, const gp_config* cfg, const gp_values* values) {
     if (!values->x) {
         set_err("%s: values.x is null", who);
         return GP_EINVAL;
@@ -392,9 +454,54 @@ int gp_ensemble_create_values(const gp_config* cfg, const gp_values* values, con
         set_err("%s: gossip has no values (cfg.algorithm is gossip)", who);
         return GP_EINVAL;
     }
+    return GP_OK;
+}
+
+int gp_ensemble_create_values(const gp_config* cfg, const gp_values* values, const gp_faults* faults,
+                              const gp_trace_cfg* trace, const uint64_t* seeds, int64_t nseeds, gp_ensemble** out) {
+    const char* who = "gp_ensemble_create_values";
+    if (!cfg || !out) {
+        set_err("%s: null argument", who);
+        return GP_EINVAL;
+    }
+    *out = nullptr;
+    if (!values) {
+        set_err("%s: values is null", who);
+        return GP_EINVAL;
+    }
+    if (values_ok(who, cfg, values)) return GP_EINVAL;
     if (trace && trace_ok(who, trace)) return GP_EINVAL;
     if (faults && faults_ok(who, faults)) return GP_EINVAL;
     return ensemble_create(cfg, values, faults, trace, seeds, nseeds, out);
+}
+
+int64_t gp_ensemble_graph_lds_bytes(const gp_graph* graph, int32_t algorithm, int32_t faults, int32_t trace) {
+    if (!pair_ok(GP_LINE, algorithm)) return GP_EINVAL;
+    const int64_t bytes = graph_image(graph, algorithm, EnsVariant{faults != 0, trace != 0});
+    return bytes < 0 ? GP_EINVAL : bytes;
+}
+
+int gp_ensemble_create_graph(const gp_config* cfg, const gp_graph* graph, const gp_values* values,
+                             const gp_faults* faults, const gp_trace_cfg* trace, const uint64_t* seeds, int64_t nseeds,
+                             gp_ensemble** out) {
+    const char* who = "gp_ensemble_create_graph";
+    if (!cfg || !out) {
+        set_err("%s: null argument", who);
+        return GP_EINVAL;
+    }
+    *out = nullptr;
+    if (!graph) {
+        set_err("%s: graph is null", who);
+        return GP_EINVAL;
+    }
+    if (cfg->topology != GP_GRAPH) {
+        set_err("%s: cfg.topology must be GP_GRAPH (got %d)", who, cfg->topology);
+        return GP_EINVAL;
+    }
+    if (values && values_ok(who, cfg, values)) return GP_EINVAL;
+    if (trace && trace_ok(who, trace)) return GP_EINVAL;
+    if (faults && faults_ok(who, faults)) return GP_EINVAL;
+    return ensemble_create(cfg, values, faults, trace, seeds, nseeds, out, graph);
 }
 
 // Rows member m has recorded: a pure function of its record, no counter lives on the device.

@@ -7,7 +7,7 @@
 
 namespace gp {
 
-template hipError_t ens_setup_t<true, false>(int, int, uint32_t);
+template hipError_t ens_setup_t<true, false>(int, int, uint32_t, uint32_t);
 template hipError_t ens_launch_t<true, false>(int, int, const EnsArgs&, uint32_t, hipStream_t);
 
 }  // namespace gp

@@ -19,6 +19,12 @@
 // half first, then lattice messages in the receiver's slot order, then random-edge
 // / full messages by ascending sender id.  Built with -ffp-contract=off.
 //
+// TOPO == GRAPH (SRS v1-G) is a fifth topology of these kernels alone:
+// the neighbour lists come from the caller's CSR, staged from HBM into LDS at the start of every
+// launch.  Gossip pushes as before; push-sum pulls: a sender publishes its target, a receiver walks
+// its in-list (transposed, ascending, deduplicated: gp_graph.hpp) and folds the senders that target
+// it, which is the canonical order.  Every line it adds sits under `if constexpr (TOPO == GRAPH)`.
+//
 // Reference mapping (Program.fs = the reference's Project2/Program.fs): the actor
 // loops Program.fs:84-131, the injector Program.fs:141-163 and the scheduler
 // Program.fs:41-61 of one run; the setup Program.fs:169-176,193,221,258-263.
@@ -215,6 +221,15 @@ __device__ __forceinline__ void trace_end(const EnsTrace& t, uint32_t m, uint32_
     if (threadIdx.x == 0) t.trec[m].sent = tr->sent;
 }
 
+// ------------------------------------------------------------------ graph (SRS v1-G)
+// Stages `bytes` (a multiple of 8: the device arrays and their LDS copies are padded alike) from
+// HBM into LDS, 8 bytes a thread and pass; the caller's next barrier publishes them.
+__device__ __forceinline__ void graph_stage(void* dst, const void* src, uint32_t bytes) {
+    uint2* d = reinterpret_cast<uint2*>(dst);
+    const uint2* s = reinterpret_cast<const uint2*>(src);
+    for (uint32_t q = threadIdx.x; q < bytes / 8u; q += blockDim.x) d[q] = s[q];
+}
+
 // ------------------------------------------------------------------ gossip
 // Per round (SRS v1 B.3): phase 1 every sending node draws a neighbour and bumps
 // inc[target] iff the target is unconverged in c, which nobody writes in this phase
@@ -241,6 +256,16 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const EnsArgs a) {
     uint32_t* dm = reinterpret_cast<uint32_t*>(at);  // FAULTS: doomed bitmap
     if (FAULTS) at += ens_up8(4 * ((P + 31) / 32));
     EnsTraceLds* tr = reinterpret_cast<EnsTraceLds*>(at);  // TRACE: trace block
+    uint32_t* goff = nullptr;  // GRAPH: out-CSR offsets, P + 1
+    uint16_t* gnbr = nullptr;  // GRAPH: out-neighbours in the caller's order
+    if constexpr (TOPO == GRAPH) {
+        if (TRACE) at += ENS_LDS_TRACE;
+        goff = reinterpret_cast<uint32_t*>(at);
+        gnbr = reinterpret_cast<uint16_t*>(at + ens_up8(4 * (P + 1)));
+        // the adjacency, redone at every launch like rnd; published by the set-up's barrier
+        graph_stage(goff, a.g_out_off, ens_up8(4 * (P + 1)));
+        graph_stage(gnbr, a.g_out_nbr, ens_up8(2 * a.g_eout));
+    }
 
     const uint32_t m = a.idx[blockIdx.x];
     Member M = member_begin(a, m);
@@ -289,7 +314,10 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const EnsArgs a) {
                 if (down_now && faults_bit(dm, i)) continue;  // (c <= 10 alone would let it send)
             if constexpr (TRACE) nsent += 1;  // it draws a target: sent, whatever becomes of the message
             uint32_t t;
-            if (TOPO == FULL) {
+            if constexpr (TOPO == GRAPH) {
+                const uint32_t o = goff[i];  // nb(i)[U_GOSSIP(deg i)]
+                t = gnbr[o + uniform(M.k0, M.k1, S_GOSSIP, i, r, goff[i + 1] - o)];
+            } else if (TOPO == FULL) {
                 t = full_target(i, uniform(M.k0, M.k1, S_GOSSIP, i, r, P - 1));
             } else {
                 const uint32_t mask = ens_mask<TOPO>(i, a.G);
@@ -402,6 +430,8 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_gossip(const EnsArgs a) {
 // FAULTS (B.5): a down node is skipped in both phases (its registers stay as they
 // are); a sender whose message is dropped or addressed to a down node halves itself
 // but publishes DIR_NONE and hooks into no list, so no receiver ever sees it.
+// GRAPH (B.7): phase A publishes tgt[i] (ENS_NONE: no message arrives from i) beside the halves;
+// phase B folds own half, then hs[n], hw[n] of every n in j's in-list with tgt[n] == j, ascending.
 // TRACE (SRS v1-T): reached = nodes with the active bit, bumped in phase B; sent counted
 // per thread in phase A; in a recording round thread 0 zeroes the err word in phase A and
 // every wave folds its nodes' |e| and its sent count in after phase B, before the closing barrier.
@@ -410,6 +440,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const EnsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr bool LISTS = TOPO == FULL || TOPO == IMP3D;
     constexpr int LT = TOPO == LINE ? LINE : GRID3D;
+    constexpr bool LATTICE = TOPO != FULL && TOPO != GRAPH;  // implicit lattice slots: mask in fl, dir[] in LDS
     constexpr uint32_t F_DOOMED = 1u << 14;  // FAULTS: fl bit, node in D
     const uint32_t P = a.G.P, tid = threadIdx.x, nthr = blockDim.x;
     uint32_t* hdr = reinterpret_cast<uint32_t*>(lds);
@@ -425,10 +456,28 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const EnsArgs a) {
     uint16_t* rnd = reinterpret_cast<uint16_t*>(at);
     if (TOPO == IMP3D) at += ens_up8(2 * P);
     uint8_t* dir = at;
-    if (TOPO != FULL) at += ens_up8(P);
+    if (LATTICE) at += ens_up8(P);
+    uint16_t* tgt = reinterpret_cast<uint16_t*>(at);  // GRAPH: this round's target of a sender whose message arrives
+    if (TOPO == GRAPH) at += ens_up8(2 * P);
     uint32_t* dm = reinterpret_cast<uint32_t*>(at);  // FAULTS: doomed bitmap
     if (FAULTS) at += ens_up8(4 * ((P + 31) / 32));
     EnsTraceLds* tr = reinterpret_cast<EnsTraceLds*>(at);  // TRACE: trace block
+    // GRAPH: out-CSR (offsets P + 1, neighbours), then the transposed, deduplicated in-CSR
+    uint32_t *goff = nullptr, *gioff = nullptr;
+    uint16_t *gnbr = nullptr, *ginbr = nullptr;
+    if constexpr (TOPO == GRAPH) {
+        if (TRACE) at += ENS_LDS_TRACE;
+        const uint32_t offb = ens_up8(4 * (P + 1)), outb = ens_up8(2 * a.g_eout);
+        goff = reinterpret_cast<uint32_t*>(at);
+        gnbr = reinterpret_cast<uint16_t*>(at + offb);
+        gioff = reinterpret_cast<uint32_t*>(at + offb + outb);
+        ginbr = reinterpret_cast<uint16_t*>(at + 2 * offb + outb);
+        // the adjacency, redone at every launch like rnd; published by the set-up's barrier
+        graph_stage(goff, a.g_out_off, ens_up8(4 * (P + 1)));
+        graph_stage(gnbr, a.g_out_nbr, ens_up8(2 * a.g_eout));
+        graph_stage(gioff, a.g_in_off, ens_up8(4 * (P + 1)));
+        graph_stage(ginbr, a.g_in_nbr, ens_up8(2 * a.g_ein));
+    }
 
     const uint32_t m = a.idx[blockIdx.x];
     Member M = member_begin(a, m);
@@ -459,7 +508,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const EnsArgs a) {
             fl[q] = gf[i];
         }
         if constexpr (TRACE) nreached += fl[q] & 1u;
-        if (TOPO != FULL) fl[q] |= ens_mask<TOPO>(i, a.G) << 8;
+        if (LATTICE) fl[q] |= ens_mask<TOPO>(i, a.G) << 8;
         if (LISTS) head[i] = ENS_NONE;
         if (TOPO == IMP3D) rnd[i] = (uint16_t)uniform(M.k0, M.k1, S_TOPO, i, 0, P - 1);
         if constexpr (FAULTS)
@@ -502,10 +551,15 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const EnsArgs a) {
             uint32_t d = DIR_NONE;
             bool sends = fl[q] & 1u;
             if constexpr (FAULTS) sends = sends && !(down_now && (fl[q] & F_DOOMED));
+            if constexpr (TOPO == GRAPH) tgt[i] = (uint16_t)ENS_NONE;  // no sender, or its message is lost
             if (sends) {
                 if constexpr (TRACE) nsent += 1;  // sent, whatever becomes of the message
                 uint32_t t = 0;
-                if (TOPO == FULL) {
+                if constexpr (TOPO == GRAPH) {
+                    d = DIR_RANDOM;  // (here: the message has a target; DIR_NONE below: it is lost)
+                    const uint32_t o = goff[i];  // nb(i)[U_PUSHSUM(deg i)]
+                    t = gnbr[o + uniform(M.k0, M.k1, S_PUSHSUM, i, r, goff[i + 1] - o)];
+                } else if (TOPO == FULL) {
                     d = DIR_RANDOM;
                     t = full_target(i, uniform(M.k0, M.k1, S_PUSHSUM, i, r, P - 1));
                 } else {
@@ -518,7 +572,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const EnsArgs a) {
                 if constexpr (FAULTS) {
                     if (a.f.q_drop != 0) gone = faults_dropped(a.f, M, i, r);
                     if (down_now && !gone) {
-                        if (TOPO != FULL && d != DIR_RANDOM) t = nbr<LT>(i, d, a.G);
+                        if (LATTICE && d != DIR_RANDOM) t = nbr<LT>(i, d, a.G);
                         gone = faults_bit(dm, t);
                     }
                 }
@@ -529,9 +583,10 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const EnsArgs a) {
                     hs[i] = s[q] * 0.5;
                     hw[i] = w[q] * 0.5;
                     if (LISTS && d == DIR_RANDOM) next[i] = (uint16_t)atomicExch(&head[t], i);
+                    if constexpr (TOPO == GRAPH) tgt[i] = (uint16_t)t;
                 }
             }
-            if (TOPO != FULL) dir[i] = (uint8_t)d;
+            if (LATTICE) dir[i] = (uint8_t)d;
         }
         __syncthreads();
 #pragma unroll
@@ -548,7 +603,19 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_pushsum(const EnsArgs a) {
             double as = (fl[q] & 1u) ? s0 * 0.5 : s0;
             double aw = (fl[q] & 1u) ? w0 * 0.5 : w0;
             bool recv = false;
-            if (TOPO != FULL) {
+            if constexpr (TOPO == GRAPH) {
+                // pull: the in-list holds the nodes that list j, ascending and each once, so the walk is
+                // the canonical fold order (B.7: every message by ascending sender id) and needs no search
+                const uint32_t e1 = gioff[j + 1];
+                for (uint32_t e = gioff[j]; e < e1; ++e) {
+                    const uint32_t n = ginbr[e];
+                    if (tgt[n] != j) continue;
+                    as = as + hs[n];
+                    aw = aw + hw[n];
+                    recv = true;
+                }
+            }
+            if (LATTICE) {
                 const uint32_t mask = (fl[q] >> 8) & 63u;
 #pragma unroll
                 for (uint32_t d = 0; d < (TOPO == LINE ? 2u : 6u); ++d) {
@@ -660,6 +727,7 @@ const void* ens_kernel(int topo, int alg, uint32_t P) {
             case FULL: return reinterpret_cast<const void*>(&k_ens_gossip<FULL, FAULTS, TRACE>);
             case GRID3D: return reinterpret_cast<const void*>(&k_ens_gossip<GRID3D, FAULTS, TRACE>);
             case IMP3D: return reinterpret_cast<const void*>(&k_ens_gossip<IMP3D, FAULTS, TRACE>);
+            case GRAPH: return reinterpret_cast<const void*>(&k_ens_gossip<GRAPH, FAULTS, TRACE>);
             default: return nullptr;
         }
     }
@@ -669,17 +737,24 @@ const void* ens_kernel(int topo, int alg, uint32_t P) {
         case FULL: return ps_kernel<FULL, FAULTS, TRACE>(npt);
         case GRID3D: return ps_kernel<GRID3D, FAULTS, TRACE>(npt);
         case IMP3D: return ps_kernel<IMP3D, FAULTS, TRACE>(npt);
+        case GRAPH: return ps_kernel<GRAPH, FAULTS, TRACE>(npt);
         default: return nullptr;
     }
 }
 
 }  // namespace
 
+// graph_lds: the image of the handle's graph (GRAPH only: its LDS size has an edge count in it).
 template <bool FAULTS, bool TRACE>
-hipError_t ens_setup_t(int topo, int alg, uint32_t P) {
+hipError_t ens_setup_t(int topo, int alg, uint32_t P, uint32_t graph_lds) {
     constexpr EnsVariant v{FAULTS, TRACE};
     const void* k = ens_kernel<FAULTS, TRACE>(topo, alg, P);
-    if (!k || P > ens_max_population(topo, alg, v)) return hipErrorInvalidValue;  // a missing kernel is an error
+    if (!k) return hipErrorInvalidValue;  // a missing kernel is an error
+    if (topo == GRAPH) {
+        if (P > ENS_GRAPH_POP_MAX || graph_lds > ENS_LDS_MAX) return hipErrorInvalidValue;
+        return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)graph_lds);
+    }
+    if (P > ens_max_population(topo, alg, v)) return hipErrorInvalidValue;
     return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ens_lds_bytes(topo, alg, P, v));
 }
 
@@ -688,13 +763,21 @@ hipError_t ens_launch_t(int topo, int alg, const EnsArgs& a, uint32_t nblocks, h
     constexpr EnsVariant v{FAULTS, TRACE};
     const uint32_t P = a.G.P;
     const void* k = ens_kernel<FAULTS, TRACE>(topo, alg, P);
-    if (!k || P > ens_max_population(topo, alg, v)) return hipErrorInvalidValue;
+    if (!k) return hipErrorInvalidValue;
+    uint64_t lds;
+    if (topo == GRAPH) {
+        lds = ens_graph_lds_bytes(alg, P, a.g_eout, a.g_ein, v);
+        if (P > ENS_GRAPH_POP_MAX || lds > ENS_LDS_MAX) return hipErrorInvalidValue;
+    } else {
+        if (P > ens_max_population(topo, alg, v)) return hipErrorInvalidValue;
+        lds = ens_lds_bytes(topo, alg, P, v);
+    }
     const uint32_t threads = ens_threads(alg, P);
     // faults_draw stores whole waves' bitmap words; the trace reduces over whole waves
     if ((FAULTS || TRACE) && threads % 64u != 0) return hipErrorInvalidValue;
     EnsArgs copy = a;
     void* args[] = {&copy};
-    return hipLaunchKernel(k, dim3(nblocks), dim3(threads), args, ens_lds_bytes(topo, alg, P, v), st);
+    return hipLaunchKernel(k, dim3(nblocks), dim3(threads), args, (size_t)lds, st);
 }
 
 }  // namespace gp

@@ -3,6 +3,8 @@
 // variant), the node slots a push-sum thread keeps and the workgroup size.  Host-clean: integer
 // arithmetic over the public enums of gossip_hip.h, nothing of HIP, so a host compiler can include it
 // (tests/helpers/ensemble_shape_check.cpp).  Included through gp_ensemble.hpp; DESIGN.md §9.
+// A caller-supplied graph (SRS v1-G) has an image of its own, ens_graph_lds_bytes,
+// with the entry counts in it; ens_lds_bytes and the caps below are the built-in topologies'.
 #pragma once
 
 #include <stdint.h>
@@ -72,6 +74,47 @@ constexpr bool ens_covers_report_range() {
 }
 static_assert(ens_covers_report_range(), "report range");
 static_assert((uint32_t)ENS_THREADS * ENS_NPT_MAX < ENS_NONE, "node ids must fit the 16-bit list links");
+
+// ---- a caller-supplied graph (SRS v1-G) ----
+// The fifth topology of the ensemble kernels; no other part of the library knows it.
+constexpr int ENS_GRAPH = GP_GRAPH;
+// Largest population of a graph: every node has a thread slot (ids then fit the 16-bit entries).
+constexpr uint32_t ENS_GRAPH_POP_MAX = (uint32_t)ENS_THREADS * ENS_NPT_MAX;
+// LDS image of one member on a graph of P nodes with e_out out-entries and e_in entries of the
+// transposed, deduplicated in-CSR (gp_graph.hpp), arrays in this order, each padded to 8 bytes:
+//   gossip   : c int32[P], inc int32[P], live bitmap u32[ceil(P/32)]
+//   push-sum : hs f64[P], hw f64[P], tgt u16[P] (this round's target of a sender whose message
+//              arrives, else ENS_NONE)
+//   then the doomed bitmap and the trace block as above, then the adjacency, staged from HBM at
+//   the start of every launch:
+//   out_off u32[P + 1], out_nbr u16[e_out]; push-sum also in_off u32[P + 1], in_nbr u16[e_in]
+// The offsets live in LDS, not in the node slots' registers: the 8-slot push-sum kernel is at its
+// register ceiling already, and the offsets cost 8 of the 26 + 4 d bytes a node of average degree d takes.
+// 64-bit: the entry counts are the caller's.
+constexpr uint64_t ens_graph_lds_bytes(int alg, uint64_t P, uint64_t e_out, uint64_t e_in, EnsVariant v) {
+    const uint64_t m8 = ~(uint64_t)7;
+    uint64_t b = ENS_LDS_HDR;
+    if (alg == GP_GOSSIP) {
+        b += ((4 * P + 7) & m8) * 2 + ((4 * ((P + 31) / 32) + 7) & m8);
+    } else {
+        b += 8 * P * 2 + ((2 * P + 7) & m8);
+    }
+    if (v.faults) b += (4 * ((P + 31) / 32) + 7) & m8;
+    if (v.trace) b += ENS_LDS_TRACE;
+    b += ((4 * (P + 1) + 7) & m8) + ((2 * e_out + 7) & m8);
+    if (alg != GP_GOSSIP) b += ((4 * (P + 1) + 7) & m8) + ((2 * e_in + 7) & m8);
+    return b;
+}
+// A symmetric graph of 1000 nodes and average degree 16 fits in every variant of both algorithms.
+constexpr bool ens_graph_covers_degree_16() {
+    for (int faults = 0; faults < 2; ++faults)
+        for (int trace = 0; trace < 2; ++trace)
+            for (int alg = GP_GOSSIP; alg <= GP_PUSHSUM; ++alg)
+                if (ens_graph_lds_bytes(alg, 1000, 16000, 16000, EnsVariant{faults != 0, trace != 0}) > ENS_LDS_MAX)
+                    return false;
+    return true;
+}
+static_assert(ens_graph_covers_degree_16(), "graph range");
 
 // Largest num_nodes: line / full P = n + 1; 3D / Imp3D the largest whole cube.
 constexpr int64_t ens_max_nodes(int topo, int alg, EnsVariant v) {

@@ -8,9 +8,9 @@
 
 namespace gp {
 
-template hipError_t ens_setup_t<false, true>(int, int, uint32_t);
+template hipError_t ens_setup_t<false, true>(int, int, uint32_t, uint32_t);
 template hipError_t ens_launch_t<false, true>(int, int, const EnsArgs&, uint32_t, hipStream_t);
-template hipError_t ens_setup_t<true, true>(int, int, uint32_t);
+template hipError_t ens_setup_t<true, true>(int, int, uint32_t, uint32_t);
 template hipError_t ens_launch_t<true, true>(int, int, const EnsArgs&, uint32_t, hipStream_t);
 
 }  // namespace gp

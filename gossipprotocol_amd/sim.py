@@ -17,6 +17,7 @@ import os
 import numpy as np
 
 from . import _lib as L
+from .graph import Graph
 
 TOPOLOGIES = ("line", "full", "3D", "Imp3D")
 ALGORITHMS = ("gossip", "push-sum")
@@ -237,6 +238,21 @@ def ensemble_max_nodes(topology: str, algorithm: str, faults: bool = False, trac
     return L.check(f(parse_topology(topology), parse_algorithm(algorithm)))
 
 
+def _gp_graph(graph: Graph) -> "L.GpGraph":
+    """The gp_graph over a :class:`Graph`'s arrays (which the Graph keeps alive)."""
+    return L.GpGraph(graph.indptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                     graph.indices.ctypes.data_as(C.POINTER(C.c_uint32)), graph.num_nodes, graph.num_edges, 0)
+
+
+def ensemble_graph_lds_bytes(graph: Graph, algorithm: str, faults: bool = False, trace: bool = False) -> int:
+    """The LDS image in bytes of one member of ``Ensemble.on_graph(graph, algorithm, ...)`` (host
+    only; gp_ensemble_graph_lds_bytes).  Raises :class:`GossipError` for an inadmissible graph, one
+    whose image exceeds what a member may take included; the message names the node and the rule,
+    or the bytes."""
+    return L.check(L.lib().gp_ensemble_graph_lds_bytes(C.byref(_gp_graph(graph)), parse_algorithm(algorithm),
+                                                       int(bool(faults)), int(bool(trace))))
+
+
 class Faults:
     """Failure model of an :class:`Ensemble` (gp_faults; SRS v1-F): every
     node but the seed node is doomed with probability ``node_fail`` and down -- silent, deaf,
@@ -329,6 +345,42 @@ class Ensemble:
             L.check(self._L.gp_ensemble_create_faults(C.byref(cfg), C.byref(f), arr, len(self.seeds), C.byref(h)),
                     self._L)
         self._h = h
+
+    @classmethod
+    def on_graph(cls, graph: Graph, algorithm: str, seeds, max_rounds: int, device: int = 0,
+                 faults: "Faults | None" = None, trace: "Trace | None" = None, values: "Values | None" = None):
+        """An ensemble on your own network (gp_ensemble_create_graph; SRS v1-G):
+        every member runs on ``graph``, a :class:`Graph`, with P = T = ``graph.num_nodes``.  Faults,
+        trace and values compose as in the constructor, and every method works on the result; its
+        ``topology`` reads "graph"."""
+        self = cls.__new__(cls)
+        self._L = L.lib()
+        self.seeds = [int(s) for s in seeds]
+        cfg = L.GpConfig()
+        cfg.num_nodes = graph.num_nodes
+        cfg.topology = L.GP_GRAPH
+        cfg.algorithm = parse_algorithm(algorithm)
+        cfg.num_gpus = 1
+        cfg.device = device
+        cfg.max_rounds = max_rounds
+        self.topology, self.algorithm, self.graph = "graph", algorithm, graph
+        self.population = graph.num_nodes
+        self.faults, self.tracing, self.values = faults, trace, values
+        arr = (C.c_uint64 * max(1, len(self.seeds)))(*self.seeds)
+        f = None if faults is None else L.GpFaults(faults.node_fail, faults.msg_drop, faults.fail_round, 0)
+        t = None if trace is None else L.GpTraceCfg(trace.stride, trace.capacity)
+        v = None
+        if values is not None:
+            dp = C.POINTER(C.c_double)
+            v = L.GpValues(values.x.ctypes.data_as(dp), None if values.w is None else values.w.ctypes.data_as(dp),
+                           len(values.x), values.mean, 0)
+        h = C.c_void_p()
+        L.check(self._L.gp_ensemble_create_graph(C.byref(cfg), C.byref(_gp_graph(graph)),
+                                                 None if v is None else C.byref(v), None if f is None else C.byref(f),
+                                                 None if t is None else C.byref(t), arr, len(self.seeds), C.byref(h)),
+                self._L)
+        self._h = h
+        return self
 
     def close(self):
         if getattr(self, "_h", None):

@@ -33,7 +33,9 @@ extern "C" {
 #define GP_MAX_POPULATION 0xFFFFF000u
 
 /* topology strings "line" | "full" | "3D" | "Imp3D" (Program.fs:180,209,238,258) */
-enum { GP_LINE = 0, GP_FULL = 1, GP_3D = 2, GP_IMP3D = 3 };
+enum { GP_LINE = 0, GP_FULL = 1, GP_3D = 2, GP_IMP3D = 3,
+       GP_GRAPH = 4 /* a caller-supplied graph: gp_ensemble_create_graph only; every other entry point
+                       that takes a topology refuses it like an unknown value, and it has no string */ };
 /* algorithm strings "gossip" | "push-sum" (Program.fs:196,202) */
 enum { GP_GOSSIP = 0, GP_PUSHSUM = 1 };
 /* gp_result.status */
@@ -382,6 +384,47 @@ int gp_set_mean(gp_sim* sim, double mean);
 int gp_ensemble_create_values(const gp_config* cfg, const gp_values* values, const gp_faults* faults,
                               const gp_trace_cfg* trace, const uint64_t* seeds, int64_t nseeds,
                               gp_ensemble** out);
+
+/* ---- Ensembles over a caller-supplied graph: SRS v1-G ---------
+ * The four topologies above are the reference's; this is yours.  A directed graph in CSR form:
+ * the neighbours of node i are indices[indptr[i] .. indptr[i + 1]) in the caller's order (the
+ * reference's NeighbourRef array).  Self-loops are allowed, duplicates are allowed and weight the
+ * pick, an undirected network lists every edge both ways.  P = T = num_nodes, no extra actor; the
+ * seed node is U_START(T).  Gossip: an active node delivers to nb(i)[U_GOSSIP(deg i)], the
+ * injector runs over {0..T-1} as for line / 3D, so a run ends whatever the graph.  Push-sum: an
+ * active node halves itself and sends to nb(i)[U_PUSHSUM(deg i)]; a receiver folds its own half
+ * first, then every message by ascending sender id.  Everything else is SRS v1 with the same
+ * streams, and the failure model, the trace and the values compose as with the built-in topologies.
+ *
+ * Admissible graphs -- checked on the host, all or nothing; gp_last_error() names the lowest
+ * offending node and the first rule it breaks:
+ *   - 2 <= num_nodes <= 8192 (one workgroup's node slots), reserved == 0;
+ *   - indptr[0] == 0, indptr non-decreasing, indptr[num_nodes] == num_edges;
+ *   - every node has degree >= 1;
+ *   - every index < num_nodes;
+ *   - the member's LDS image, adjacency included, fits (gp_ensemble_graph_lds_bytes; the error
+ *     names the bytes it would need).
+ * A graph that is not strongly connected is admissible: push-sum on it ends at max_rounds. */
+typedef struct gp_graph {       /* blittable */
+    const int64_t* indptr;      /* num_nodes + 1 entries */
+    const uint32_t* indices;    /* num_edges entries */
+    int64_t num_nodes;
+    int64_t num_edges;
+    int64_t reserved;           /* 0 */
+} gp_graph;
+
+/* The LDS image in bytes of one member on this graph (host only, no GPU): validates the graph and
+ * returns the size, or GP_EINVAL for an inadmissible graph or pair -- one whose image exceeds the
+ * 150 KiB a member may take included.  faults / trace != 0: with a failure model / a trace. */
+int64_t gp_ensemble_graph_lds_bytes(const gp_graph* graph, int32_t algorithm, int32_t faults, int32_t trace);
+/* An ensemble on the graph: cfg->topology must be GP_GRAPH and cfg->num_nodes == graph->num_nodes.
+ * values (push-sum only), faults and trace may be NULL; every check of gp_ensemble_create,
+ * _create_faults, _create_traced and _create_values applies to what is given.  The arrays are
+ * copied: the caller may free them after the call.  The handle works with every gp_ensemble_* call;
+ * the summaries' default mean is (P - 1) / 2. */
+int gp_ensemble_create_graph(const gp_config* cfg, const gp_graph* graph, const gp_values* values,
+                             const gp_faults* faults, const gp_trace_cfg* trace, const uint64_t* seeds,
+                             int64_t nseeds, gp_ensemble** out);
 
 #ifdef __cplusplus
 }
